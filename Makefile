@@ -12,7 +12,7 @@ test-gpu:
 	$(PY) -m pytest tests -q -m gpu
 
 bench:
-	$(PY) bench.py --steps 10 --warmup 3
+	$(PY) bench.py --steps 10 --warmup 3 --full
 
 serve:
 	$(PY) -m code_intelligence_amd.serve.app --model_path $(MODEL_PATH)

@@ -9,6 +9,9 @@ per-GPU batch 512 x seq 512 (BASELINE.json configs 2-3: global bs 4096 at
 DP=8, weak scaling).
 
 Single GPU:      python bench.py --gpus 1 --steps 20 --warmup 5
+                 (plain run: set up, warm up, time the steps, print the line)
+Everything else: add --full (quick serve sub-benchmark in the same line)
+Outputs:         add --dump-outputs DIR (last timed step, as DIR/<name>.npy)
 Multi GPU (DP):  python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
                      --master-addr 127.0.0.1 bench.py --gpus N ...
 """
@@ -58,6 +61,14 @@ def parse_args():
                         "JSON line instead of the LM training line")
     p.add_argument("--no-serve", action="store_true",
                    help="skip the serve sub-benchmark in the LM line")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beyond the headline figure "
+                        "(the quick serve sub-benchmark carried in the LM "
+                        "line); off by default so a plain run stays lean")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps write what the last timed "
+                        "step computed (loss, hidden state, updated "
+                        "parameters) as DIR/<name>.npy")
     return p.parse_args()
 
 
@@ -116,6 +127,34 @@ def serve_bench(args, quick: bool = True) -> dict:
     }
 
 
+# per-tensor element cap of --dump-outputs: ~30 tensors x 256k x 4 B stays
+# far below 64 MB for any model size
+_DUMP_MAX_ELEMS = 1 << 18
+
+
+def dump_outputs(out_dir: str, loss: float, model) -> None:
+    """Write what a caller of the timed path holds after its last step: the
+    step's loss, the carried hidden state and the updated parameters.
+    float32 .npy (loss float64); tensors above _DUMP_MAX_ELEMS elements are
+    reduced to a fixed seeded sample of their flattened elements, the same
+    indices on every run."""
+    import numpy as np
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "loss.npy", np.asarray([loss], dtype=np.float64))
+    named = [(f"param.{n}", p) for n, p in model.named_parameters()]
+    for l, (h, c) in enumerate(model.encoder.hidden):
+        named += [(f"hidden.{l}.h", h), (f"hidden.{l}.c", c)]
+    g = torch.Generator().manual_seed(4321)
+    for name, t in named:
+        flat = t.detach().reshape(-1)
+        if flat.numel() > _DUMP_MAX_ELEMS:
+            idx = torch.randint(0, flat.numel(), (_DUMP_MAX_ELEMS,),
+                                generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(d / f"{name}.npy", flat.float().cpu().numpy())
+
+
 def main():
     args = parse_args()
     if args.lstm_mode:
@@ -142,7 +181,7 @@ def main():
     rank, world = init_distributed()
     on_gpu = torch.cuda.is_available()
     serve = None
-    if rank == 0 and world == 1 and not args.no_serve:
+    if args.full and rank == 0 and world == 1 and not args.no_serve:
         # BASELINE.json's metric names BOTH halves ("LM tokens/sec ... and
         # issue-embeddings/sec served"): measure serving FIRST, before the
         # sustained training burst drags clocks down.
@@ -190,16 +229,20 @@ def main():
             torch.cuda.synchronize()
 
     barrier_sync()
+    last_loss = float("nan")
     t0 = time.perf_counter()
     for i in range(args.steps):
         x, y = batch(args.warmup + i)
-        trainer.train_step(x, y, lr)
+        last_loss = trainer.train_step(x, y, lr)
     barrier_sync()
     elapsed = time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([elapsed], device=device if on_gpu else None)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t)
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_loss, model)
 
     n_gpus = world if on_gpu else args.gpus
     tokens = args.bs * args.seq * args.steps * world

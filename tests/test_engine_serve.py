@@ -100,6 +100,10 @@ def test_serve_model_uri_resolution(tmp_path, monkeypatch):
     from code_intelligence_amd.text.tokenizer import Vocab, defaults_specials
     store = ObjectStore(root=tmp_path / "store")
     monkeypatch.setattr(gcs, "_default_store", store)
+    # the download cache lives under the system temp dir: point that at this
+    # test's own directory so no shared, possibly foreign-owned path is used
+    import tempfile
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path))
     model = AWDLSTM(vocab_sz=20, emb_sz=8, n_hid=12, n_layers=1)
     local = tmp_path / "art"
     save_artifacts(model, Vocab(defaults_specials), local)

@@ -130,6 +130,54 @@ def test_bench_contract_cpu_fallback():
     assert {"model", "global_batch", "seq_len", "parallelism"} <= set(out["config"])
 
 
+@pytest.mark.timeout(300)
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last timed step's results as float .npy
+    files that are identical from run to run; a plain run carries no serve
+    object, --full does, and --full leaves the timed path's results alone."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from pathlib import Path
+    import numpy as np
+    root = Path(__file__).resolve().parents[1]
+
+    # the options are host-side plumbing: hide any GPU from the child so the
+    # small CPU config runs everywhere and the results compare exactly
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
+
+    def run(out_dir, *extra):
+        r = subprocess.run([sys.executable, str(root / "bench.py"),
+                            "--gpus", "1", "--steps", "2", "--warmup", "1",
+                            "--dump-outputs", str(out_dir), *extra],
+                           capture_output=True, text=True, timeout=140,
+                           env=env)
+        assert r.returncode == 0, r.stderr[-800:]
+        lines = [l for l in r.stdout.strip().splitlines()
+                 if l.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    plain = run(tmp_path / "a")
+    full = run(tmp_path / "b", "--full")
+    assert "serve" not in plain and "serve" in full
+    assert plain["steps"] == 2 and plain["ms_per_step"] > 0
+    files = sorted(p.name for p in (tmp_path / "a").glob("*.npy"))
+    assert "loss.npy" in files
+    assert any(f.startswith("param.") for f in files)
+    assert any(f.startswith("hidden.") for f in files)
+    assert files == sorted(p.name for p in (tmp_path / "b").glob("*.npy"))
+    total = 0
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64), (f, a.dtype)
+        assert np.isfinite(a).all(), f
+        assert np.array_equal(a, b), f
+        total += a.nbytes
+    assert total <= 64 * 2 ** 20
+
+
 @pytest.mark.timeout(420)
 def test_bench_world8_torchrun_cpu():
     """Launch bench.py EXACTLY like the driver's 8-GPU scale run
