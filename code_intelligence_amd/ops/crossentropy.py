@@ -18,6 +18,13 @@ full 2.5e13-FLOP GEMM per step). If the allocation does not fit
 (CI_CE_SAVE_LOGITS=0 or OOM), it falls back to recompute-in-backward with
 only O(B·T) state saved.
 
+fp8 path, one-pass epilogue: when a second resident (B·T, 60k) e4m3 buffer
+(~16 GB) also fits, forward's epilogue kernel reads each logits row ONCE
+from registers for the logsumexp AND both dlogits forms (bf16 in place,
+e4m3 copy), so backward runs no epilogue pass at all: measured 417.1 vs
+422.1 ms/step (profiles/BENCH_HISTORY.md). Rows wider than the kernel's
+register cache, unaligned shapes and OOM keep the two-kernel path.
+
 CPU path: plain F.cross_entropy composition (numerics reference)."""
 from __future__ import annotations
 
@@ -61,6 +68,10 @@ def _fp8r_enabled() -> bool:
 
 
 _STORE = 448.0  # fixed dlogits store scale: |softmax - onehot| <= 1
+
+# ce_onepass_dual caches one bf16 row in registers: 256 threads x 32
+# 16-byte vectors (ce.hip kOnepassMaxVec); wider rows take two kernels
+_ONEPASS_MAX_V = 256 * 32 * 8
 
 _ce_side = None
 
@@ -113,6 +124,22 @@ class _FusedCEFp8Function(torch.autograd.Function):
                 logits_full = torch.empty(N, V, dtype=h.dtype, device=dev)
             except torch.cuda.OutOfMemoryError:
                 pass
+        # one-pass epilogue: with a second resident (N, V) e4m3 buffer the
+        # row is read ONCE here (lse + both dlogits forms, scaled 1/N) and
+        # backward runs no epilogue at all. Needs every chunk on the fp8
+        # GEMM path and the row within the kernel's register cache.
+        dlog8_full = None
+        if logits_full is not None and V <= _ONEPASS_MAX_V \
+                and H % 16 == 0 and V % 16 == 0 \
+                and N % 16 == 0 and min(C, N) % 16 == 0:
+            try:
+                dlog8_full = torch.empty(N, V, dtype=f8, device=dev)
+            except torch.cuda.OutOfMemoryError:
+                pass
+        onepass = dlog8_full is not None
+        if onepass:
+            inv_n = (torch.ones((), dtype=torch.float32, device=dev)
+                     / N).reshape(1)
         scratch = None if logits_full is not None else \
             torch.empty(min(C, N), V, dtype=h.dtype, device=dev)
         for s in range(0, N, C):
@@ -124,8 +151,14 @@ class _FusedCEFp8Function(torch.autograd.Function):
                                  out_dtype=h.dtype, out=logits)
             else:  # tail/odd shapes: bf16 GEMM
                 torch.mm(h[s:e], w_t, out=logits)
-            lib.ce_rowstats(logits, tgt64[s:e], b32, lse[s:e],
-                            tgt_logit[s:e])
+            if onepass:
+                # logits <- bf16((softmax-onehot)/N) in place,
+                # dlog8_full <- e4m3((softmax-onehot)*448), lse out
+                lib.ce_onepass_dual(logits, tgt64[s:e], b32, lse[s:e],
+                                    inv_n, dlog8_full[s:e], _STORE)
+            else:
+                lib.ce_rowstats(logits, tgt64[s:e], b32, lse[s:e],
+                                tgt_logit[s:e])
         # exact target logits (bf16 gather-dot, fp32 accumulation): the
         # loss value must not carry fp8 input-quantization target error
         wrows = weight.detach()[tgt64]
@@ -135,6 +168,8 @@ class _FusedCEFp8Function(torch.autograd.Function):
         loss = (lse - tgt_logit).mean()
         ctx.save_for_backward(h, weight, b32, tgt64, lse, w8, sw)
         ctx.logits_full = logits_full
+        ctx.dlog8_full = dlog8_full
+        ctx.chunk = C
         ctx.has_bias = bias is not None
         ctx.bias_dtype = bias.dtype if bias is not None else None
         return loss
@@ -146,15 +181,21 @@ class _FusedCEFp8Function(torch.autograd.Function):
         h, weight, b32, targets, lse, w8, sw = ctx.saved_tensors
         logits_full = ctx.logits_full
         ctx.logits_full = None
+        # set by forward's one-pass epilogue: logits_full already holds
+        # bf16 (softmax-onehot)/N and dlog8_full its e4m3*448 copy
+        dlog8_full = ctx.dlog8_full
+        ctx.dlog8_full = None
+        onepass = dlog8_full is not None
         has_bias = ctx.has_bias
         N, H = h.shape
         V = weight.shape[0]
-        C = _FusedCEFunction.CHUNK
+        C = ctx.chunk if onepass else _FusedCEFunction.CHUNK
         dev = h.device
         dh = torch.empty_like(h)
         scale = (dloss / N).to(torch.float32).reshape(1)
         sc_over_store = (scale.reshape(()) / _STORE)
-        scratch8 = torch.empty(min(C, N), V, dtype=f8, device=dev)
+        scratch8 = None if onepass else \
+            torch.empty(min(C, N), V, dtype=f8, device=dev)
         # db folded into the dW GEMM: h gains a 16-column pad whose first
         # extra column is ones, so column H of dW_aug IS sum(dlog) — the
         # separate db reduction re-read the whole dlog chunk (7.9 GB at
@@ -183,12 +224,16 @@ class _FusedCEFp8Function(torch.autograd.Function):
             else:
                 dlog = recompute[:c]
                 torch.mm(h[s:e], w_t, out=dlog)
-            # dlog <- bf16((softmax-onehot)*dloss/N) in place;
-            # scratch8 <- e4m3((softmax-onehot)*448) in the same read
-            lib.ce_dlogits_dual(dlog, targets[s:e], bias_arg, lse[s:e],
-                                scale, scratch8, _STORE)
+            if onepass:
+                dlog8 = dlog8_full[s:e]
+            else:
+                # dlog <- bf16((softmax-onehot)*dloss/N) in place;
+                # scratch8 <- e4m3((softmax-onehot)*448) in the same read
+                lib.ce_dlogits_dual(dlog, targets[s:e], bias_arg, lse[s:e],
+                                    scale, scratch8, _STORE)
+                dlog8 = scratch8[:c]
             if c % 16 == 0 and H % 16 == 0 and V % 16 == 0:
-                torch._scaled_mm(scratch8[:c], w8_cm, scale_a=sc_over_store,
+                torch._scaled_mm(dlog8, w8_cm, scale_a=sc_over_store,
                                  scale_b=sw, out_dtype=h.dtype, out=dh[s:e])
             else:
                 torch.mm(dlog, weight, out=dh[s:e])
@@ -204,6 +249,15 @@ class _FusedCEFp8Function(torch.autograd.Function):
             main.wait_stream(side)
         dw = dw_aug[:, :H]
         db = dw_aug[:, H] if has_bias else None
+        if onepass:
+            # the stored bf16 dlogits carry 1/N, not dloss/N: apply dloss
+            # to the fp32 sums inside the casts that run anyway (x*1 is
+            # exact, so dloss == 1 reproduces the two-kernel path's bits)
+            dl = dloss.to(torch.float32)
+            dw_out = torch.empty(V, H, dtype=weight.dtype, device=dev)
+            torch.mul(dw, dl, out=dw_out)
+            return (dh, dw_out,
+                    (db * dl).to(ctx.bias_dtype) if has_bias else None, None)
         return (dh, dw.to(weight.dtype),
                 db.to(ctx.bias_dtype) if has_bias else None, None)
 

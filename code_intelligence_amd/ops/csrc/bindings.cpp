@@ -41,6 +41,9 @@ void ce_dlogits(at::Tensor logits, at::Tensor targets, at::Tensor bias,
 void ce_dlogits_dual(at::Tensor logits, at::Tensor targets, at::Tensor bias,
                      at::Tensor lse, at::Tensor scale, at::Tensor scratch8,
                      double store_scale);
+void ce_onepass_dual(at::Tensor logits, at::Tensor targets, at::Tensor bias,
+                     at::Tensor lse, at::Tensor scale, at::Tensor out8,
+                     double store_scale);
 at::Tensor artar_forward(at::Tensor out, at::Tensor r);
 std::vector<at::Tensor> artar_backward(at::Tensor out, at::Tensor r,
                                        at::Tensor dloss, double ca, double cb);
@@ -85,6 +88,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_dlogits", &ci::ce_dlogits, "in-place (softmax-onehot)*scale");
   m.def("ce_dlogits_dual", &ci::ce_dlogits_dual,
         "in-place bf16 dlogits + e4m3 scratch copy for the fp8 dh GEMM");
+  m.def("ce_onepass_dual", &ci::ce_onepass_dual,
+        "one read of the row: lse + in-place bf16 dlogits + e4m3 copy");
   m.def("artar_forward", &ci::artar_forward,
         "fused AR/TAR partial sums (one pass over out and r)");
   m.def("artar_backward", &ci::artar_backward,

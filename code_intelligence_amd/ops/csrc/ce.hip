@@ -271,4 +271,213 @@ void ce_dlogits_dual(at::Tensor logits, at::Tensor targets, at::Tensor bias,
   });
 }
 
+// ---- one-pass CE epilogue -------------------------------------------------
+// ce_rowstats + ce_dlogits_dual read the same logits row twice (once in
+// forward for lse, once in backward for dlogits). A 60k bf16 row is 7500
+// 16-B vectors = 30 per thread of a 256-thread block, so the whole row fits
+// in VGPRs: load it once, reduce to lse, then write both dlogits forms from
+// the registers. The arithmetic of both phases is the two kernels' above,
+// element for element and in the same order, so lse, the bf16 buffer and
+// the e4m3 bytes are bit-identical to the two-kernel path.
+constexpr int kOnepassMaxVec = 32;  // cached 16-B vectors per thread
+
+// bf16 -> fp32 is a 16-bit shift; done on whole registers (no pointer
+// punning) so the cached row stays 4 registers per vector
+static __device__ __forceinline__ void unpack_bf16x8(const uint4& c,
+                                                     float* out) {
+  out[0] = __uint_as_float(c.x << 16); out[1] = __uint_as_float(c.x & 0xffff0000u);
+  out[2] = __uint_as_float(c.y << 16); out[3] = __uint_as_float(c.y & 0xffff0000u);
+  out[4] = __uint_as_float(c.z << 16); out[5] = __uint_as_float(c.z & 0xffff0000u);
+  out[6] = __uint_as_float(c.w << 16); out[7] = __uint_as_float(c.w & 0xffff0000u);
+}
+
+template <int THREADS, bool HAS_BIAS>
+__global__ __launch_bounds__(THREADS) void ce_onepass_dual_kernel(
+    __hip_bfloat16* __restrict__ logits, long row_stride,
+    const long* __restrict__ targets, const float* __restrict__ bias,
+    float* __restrict__ lse, const float* __restrict__ scale,
+    unsigned char* __restrict__ out8, long srs, float store_scale, int V) {
+  // lse must equal ce_rowstats_kernel's to the bit, so nothing here may be
+  // left to the compiler's choice of which a*b+c to fuse: contraction is
+  // off in this body and the merges below spell out the fused / unfused
+  // forms that ce_rowstats_kernel compiles to for gfx950.
+  #pragma clang fp contract(off)
+  using T = __hip_bfloat16;
+  constexpr int NW = THREADS / kWave;
+  constexpr int VEC = 8;
+  const int row = blockIdx.x;
+  T* x = logits + (long)row * row_stride;
+  unsigned char* s8 = out8 + (long)row * srs;
+  __shared__ float red_m[NW];
+  __shared__ float red_s[NW];
+  __shared__ float lse_sh;
+  const int Vv = V / VEC * VEC;
+  // All loads first (compile-time indices keep the cache in registers).
+  // No branch here: a slot past the row end re-reads the row's last
+  // vector (Vv >= VEC is the wrapper's check; a cache hit that is never
+  // used), so the loads stay unpredicated and issue back to back.
+  uint4 cache[kOnepassMaxVec];
+  #pragma unroll
+  for (int k = 0; k < kOnepassMaxVec; ++k) {
+    const int v = (threadIdx.x + k * THREADS) * VEC;
+    cache[k] = *reinterpret_cast<const uint4*>(x + min(v, Vv - VEC));
+  }
+  // Opaque barrier for the compiler (emits nothing): without it the bf16
+  // unpack of phase 1 is hoisted up to each load, which serializes the
+  // loads behind a wait each and doubles the live registers.
+  #pragma unroll
+  for (int k = 0; k < kOnepassMaxVec; ++k)
+    asm volatile("" : "+v"(cache[k].x), "+v"(cache[k].y), "+v"(cache[k].z),
+                      "+v"(cache[k].w));
+  // phase 1: ce_rowstats_kernel's online (max, sum) over the cached row
+  float v8[VEC], b8[VEC];
+  float m = -3.4e38f, sum = 0.f;
+  #pragma unroll
+  for (int k = 0; k < kOnepassMaxVec; ++k) {
+    const int v = (threadIdx.x + k * THREADS) * VEC;
+    if (v < Vv) {
+      unpack_bf16x8(cache[k], v8);
+      if (HAS_BIAS) {
+        load_bias<VEC>(bias + v, b8);
+        #pragma unroll
+        for (int e = 0; e < VEC; ++e) v8[e] += b8[e];
+      }
+      float bm = v8[0];
+      #pragma unroll
+      for (int e = 1; e < VEC; ++e) bm = fmaxf(bm, v8[e]);
+      if (bm > m) {
+        sum *= __expf(m - bm);
+        m = bm;
+      }
+      #pragma unroll
+      for (int e = 0; e < VEC; ++e) sum += __expf(v8[e] - m);
+    }
+  }
+  for (int v = Vv + threadIdx.x; v < V; v += THREADS) {
+    const float val = ld(x + v) + (HAS_BIAS ? bias[v] : 0.f);
+    if (val > m) {
+      sum *= __expf(m - val);
+      m = val;
+    }
+    sum += __expf(val - m);
+  }
+  #pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) {
+    const float om = __shfl_down(m, off);
+    const float os = __shfl_down(sum, off);
+    const float nm = fmaxf(m, om);
+    const float t = os * __expf(om - nm);
+    // one fused multiply-add per step, except the last (two products)
+    sum = off > 1 ? __builtin_fmaf(sum, __expf(m - nm), t)
+                  : sum * __expf(m - nm) + t;
+    m = nm;
+  }
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    red_m[threadIdx.x / kWave] = m;
+    red_s[threadIdx.x / kWave] = sum;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float gm = red_m[0];
+    for (int w = 1; w < NW; ++w) gm = fmaxf(gm, red_m[w]);
+    float gs = 0.f;
+    for (int w = 0; w < NW; ++w) gs += red_s[w] * __expf(red_m[w] - gm);
+    const float r = gm + __logf(gs);
+    lse[row] = r;
+    lse_sh = r;
+  }
+  __syncthreads();
+  // Make the cached row and the bias pointer opaque again (no instruction
+  // is emitted), so phase 2 re-derives x + bias from the 128 cached
+  // registers and the compiler has no reason to keep phase 1's 256
+  // unpacked fp32 values alive across the barrier.
+  #pragma unroll
+  for (int k = 0; k < kOnepassMaxVec; ++k)
+    asm volatile("" : "+v"(cache[k].x), "+v"(cache[k].y), "+v"(cache[k].z),
+                      "+v"(cache[k].w));
+  const float* bias2 = bias;
+  asm volatile("" : "+s"(bias2));
+  // phase 2: ce_dlogits_dual_kernel's transform from the cached row
+  const float l = lse_sh;
+  const float sc = scale[0];
+  const int tgt = (int)targets[row];
+  #pragma unroll
+  for (int k = 0; k < kOnepassMaxVec; ++k) {
+    const int v = (threadIdx.x + k * THREADS) * VEC;
+    if (v < Vv) {
+      unpack_bf16x8(cache[k], v8);
+      if (HAS_BIAS) {
+        load_bias<VEC>(bias2 + v, b8);
+        #pragma unroll
+        for (int e = 0; e < VEC; ++e) v8[e] += b8[e];
+      }
+      T buf[VEC];
+      unsigned char q8[VEC];
+      #pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        float p = __expf(v8[e] - l);
+        if (v + e == tgt) p -= 1.f;
+        st(buf + e, p * sc);
+        q8[e] = __hip_fp8_e4m3(p * store_scale).__x;
+      }
+      *reinterpret_cast<int4*>(x + v) = *reinterpret_cast<const int4*>(buf);
+      *reinterpret_cast<uint2*>(s8 + v) = *reinterpret_cast<const uint2*>(q8);
+    }
+  }
+  for (int v = Vv + threadIdx.x; v < V; v += THREADS) {
+    float p = __expf(ld(x + v) + (HAS_BIAS ? bias2[v] : 0.f) - l);
+    if (v == tgt) p -= 1.f;
+    st(x + v, p * sc);
+    s8[v] = __hip_fp8_e4m3(p * store_scale).__x;
+  }
+}
+
+void ce_onepass_dual(at::Tensor logits, at::Tensor targets, at::Tensor bias,
+                     at::Tensor lse, at::Tensor scale, at::Tensor out8,
+                     double store_scale) {
+  CI_CHECK_CUDA(logits); CI_CHECK_CONTIG(logits); CI_CHECK_CONTIG(out8);
+  CI_CHECK_CUDA(targets); CI_CHECK_CUDA(lse); CI_CHECK_CUDA(scale);
+  CI_CHECK_CUDA(out8);
+  TORCH_CHECK(logits.dim() == 2 && out8.dim() == 2);
+  TORCH_CHECK(logits.scalar_type() == at::ScalarType::BFloat16,
+              "ce_onepass_dual: bf16 logits only");
+  constexpr int THREADS = 256;
+  const int N = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V >= 8, "ce_onepass_dual: V must hold one 16-byte vector");
+  TORCH_CHECK(V / 8 <= kOnepassMaxVec * THREADS,
+              "ce_onepass_dual: V=", V, " exceeds the register-cached row (",
+              kOnepassMaxVec * THREADS * 8, ")");
+  TORCH_CHECK(out8.size(0) >= N && out8.size(1) == V,
+              "ce_onepass_dual: fp8 output too small");
+  TORCH_CHECK(out8.scalar_type() == at::ScalarType::Byte ||
+              out8.scalar_type() == at::ScalarType::Float8_e4m3fn);
+  TORCH_CHECK(targets.scalar_type() == at::ScalarType::Long &&
+              targets.numel() >= N && lse.numel() >= N &&
+              lse.scalar_type() == at::ScalarType::Float &&
+              scale.scalar_type() == at::ScalarType::Float &&
+              scale.numel() >= 1);
+  const bool hb = bias.numel() > 0;
+  TORCH_CHECK(!hb || (bias.is_cuda() && bias.numel() >= V &&
+                      bias.scalar_type() == at::ScalarType::Float));
+  if (N == 0) return;
+  using T = __hip_bfloat16;
+  if (hb) {
+    hipLaunchKernelGGL((ce_onepass_dual_kernel<THREADS, true>),
+        dim3(N), dim3(THREADS), 0, stream(),
+        reinterpret_cast<T*>(logits.data_ptr()), (long)V,
+        targets.data_ptr<long>(), bias.data_ptr<float>(),
+        lse.data_ptr<float>(), scale.data_ptr<float>(),
+        reinterpret_cast<unsigned char*>(out8.data_ptr()),
+        (long)V, (float)store_scale, V);
+  } else {
+    hipLaunchKernelGGL((ce_onepass_dual_kernel<THREADS, false>),
+        dim3(N), dim3(THREADS), 0, stream(),
+        reinterpret_cast<T*>(logits.data_ptr()), (long)V,
+        targets.data_ptr<long>(), nullptr,
+        lse.data_ptr<float>(), scale.data_ptr<float>(),
+        reinterpret_cast<unsigned char*>(out8.data_ptr()),
+        (long)V, (float)store_scale, V);
+  }
+}
+
 }  // namespace ci

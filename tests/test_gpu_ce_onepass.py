@@ -1,0 +1,170 @@
+"""One-pass CE epilogue (ce_onepass_dual) vs the two-kernel path it replaces
+(ce_rowstats + ce_dlogits_dual). The new kernel runs the same arithmetic in
+the same order from a register-cached row, so lse, the bf16 dlogits and the
+e4m3 bytes must be bit-identical: every kernel-level check is torch.equal."""
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+ROWS = 32
+STORE = 448.0
+# 2048: exactly one 16-byte vector per thread; 2056: some threads get a
+# second vector; 2051: scalar tail; 40: most threads idle; 65536: the
+# register bound (32 vectors per thread)
+SHAPES = [2048, 2056, 2051, 40, 65536]
+OVER_BOUND = 65544
+
+
+def _lib():
+    from code_intelligence_amd.ops import extension as ext
+    return ext.require()
+
+
+def _inputs(V, bias, tgt_col, shift=0.0, seed=0):
+    g = torch.Generator().manual_seed(seed + V)
+    logits = (torch.randn(ROWS, V, generator=g) * 3 + shift) \
+        .to(torch.bfloat16).to(DEV)
+    b = (torch.randn(V, generator=g) * 0.5).to(DEV) if bias \
+        else torch.empty(0, dtype=torch.float32, device=DEV)
+    tgt = torch.full((ROWS,), tgt_col, dtype=torch.int64, device=DEV)
+    scale = torch.full((1,), 1.0 / ROWS, dtype=torch.float32, device=DEV)
+    return logits, b, tgt, scale
+
+
+def _two_kernel(lib, logits, b, tgt, scale):
+    x = logits.clone()
+    V = x.shape[1]
+    lse = torch.empty(ROWS, dtype=torch.float32, device=DEV)
+    tl = torch.empty(ROWS, dtype=torch.float32, device=DEV)
+    q = torch.zeros(ROWS, V, dtype=torch.uint8, device=DEV)
+    lib.ce_rowstats(x, tgt, b, lse, tl)
+    lib.ce_dlogits_dual(x, tgt, b, lse, scale, q, STORE)
+    return lse, x, q
+
+
+def _one_pass(lib, logits, b, tgt, scale):
+    x = logits.clone()
+    V = x.shape[1]
+    lse = torch.empty(ROWS, dtype=torch.float32, device=DEV)
+    q = torch.zeros(ROWS, V, dtype=torch.uint8, device=DEV)
+    lib.ce_onepass_dual(x, tgt, b, lse, scale, q, STORE)
+    return lse, x, q
+
+
+def _assert_same(old, new):
+    for name, a, b in zip(("lse", "bf16 dlogits", "e4m3 bytes"), old, new):
+        assert torch.isfinite(a.float()).all(), name
+        assert torch.equal(a.view(torch.int16) if a.dtype == torch.bfloat16
+                           else a,
+                           b.view(torch.int16) if b.dtype == torch.bfloat16
+                           else b), name
+
+
+@pytest.mark.parametrize("last_col", [False, True])
+@pytest.mark.parametrize("bias", [False, True])
+@pytest.mark.parametrize("V", SHAPES)
+def test_onepass_bit_identical(V, bias, last_col):
+    lib = _lib()
+    args = _inputs(V, bias, V - 1 if last_col else 0)
+    _assert_same(_two_kernel(lib, *args), _one_pass(lib, *args))
+
+
+def test_onepass_shifted_logits():
+    # +80: sum(exp(x)) overflows fp32 without the running-max subtraction
+    # (_assert_same also requires every output finite)
+    lib = _lib()
+    args = _inputs(2056, True, 5, shift=80.0)
+    _assert_same(_two_kernel(lib, *args), _one_pass(lib, *args))
+
+
+@pytest.mark.parametrize("bias", [False, True])
+def test_onepass_refuses_row_over_register_bound(bias):
+    lib = _lib()
+    logits, b, tgt, scale = _inputs(OVER_BOUND, bias, 0)
+    lse = torch.empty(ROWS, dtype=torch.float32, device=DEV)
+    q = torch.zeros(ROWS, OVER_BOUND, dtype=torch.uint8, device=DEV)
+    before = logits.clone()
+    with pytest.raises(RuntimeError, match="register-cached"):
+        lib.ce_onepass_dual(logits, tgt, b, lse, scale, q, STORE)
+    assert torch.equal(logits.view(torch.int16), before.view(torch.int16))
+
+
+def test_onepass_refuses_fp32_logits():
+    lib = _lib()
+    logits, b, tgt, scale = _inputs(2048, False, 0)
+    lse = torch.empty(ROWS, dtype=torch.float32, device=DEV)
+    q = torch.zeros(ROWS, 2048, dtype=torch.uint8, device=DEV)
+    with pytest.raises(RuntimeError, match="bf16"):
+        lib.ce_onepass_dual(logits.float(), tgt, b, lse, scale, q, STORE)
+
+
+def _run_ce(V, dloss_half, seed=3):
+    from code_intelligence_amd.ops.crossentropy import tied_decoder_ce
+    N, H = 64, 32
+    g = torch.Generator().manual_seed(seed)
+    h = (torch.randn(N, H, generator=g) * 0.5).to(DEV, torch.bfloat16) \
+        .requires_grad_(True)
+    w = (torch.randn(V, H, generator=g) * 0.2).to(DEV, torch.bfloat16) \
+        .requires_grad_(True)
+    b = (torch.randn(V, generator=g) * 0.1).to(DEV, torch.bfloat16) \
+        .requires_grad_(True)
+    t = torch.randint(0, V, (N,), generator=g).to(DEV)
+    t[0], t[1] = 0, V - 1
+    loss = tied_decoder_ce(h, w, b, t)
+    (loss * 0.5 if dloss_half else loss).backward()
+    return [x.detach().float() for x in (loss, h.grad, w.grad, b.grad)]
+
+
+# 2056 and 2064 both give some threads a second vector; 2064 is a multiple
+# of 16, which the fp8 GEMMs (and therefore the one-pass path) need, 2056
+# is not and must take the unchanged two-kernel path. 65544 / 65552 are the
+# same pair over the register bound: both must fall back.
+@pytest.mark.parametrize("dloss_half", [False, True])
+@pytest.mark.parametrize("V,expect_onepass", [(2056, False), (2064, True),
+                                              (65544, False), (65552, False)])
+def test_tied_decoder_ce_matches_two_kernel_path(V, expect_onepass,
+                                                 dloss_half, monkeypatch):
+    lib = _lib()
+    calls = []
+    real = lib.ce_onepass_dual
+
+    def counting(*a):
+        calls.append(1)
+        return real(*a)
+
+    monkeypatch.setattr(lib, "ce_onepass_dual", counting)
+    from code_intelligence_amd.ops import crossentropy as ce_mod
+    monkeypatch.setenv("CI_CE_FP8R", "1")
+    # reference = the two-kernel code path. Unaligned V: CI_CE_SAVE_LOGITS=0
+    # (forward and the backward recompute both run the bf16 GEMM there, so
+    # the logits are the same). Aligned V: that switch would also swap the
+    # fp8 forward GEMM's logits for a bf16 recompute, so keep the resident
+    # logits and only rule the one-pass kernel out through its V bound.
+    with monkeypatch.context() as mp:
+        if V % 16:
+            mp.setenv("CI_CE_SAVE_LOGITS", "0")
+        else:
+            mp.setattr(ce_mod, "_ONEPASS_MAX_V", 0)
+        ref = _run_ce(V, dloss_half)
+    assert not calls
+    monkeypatch.setenv("CI_CE_SAVE_LOGITS", "1")
+    new = _run_ce(V, dloss_half)
+    assert bool(calls) == expect_onepass
+    loss_r, dh_r, dw_r, db_r = ref
+    loss_n, dh_n, dw_n, db_n = new
+    # loss never depends on the stored dlogits; dh reads the e4m3 copy,
+    # whose bytes and GEMM scale (dloss/(N*448)) are the same on both paths
+    assert torch.equal(loss_r, loss_n)
+    assert torch.equal(dh_r, dh_n)
+    if not dloss_half:
+        assert torch.equal(dw_r, dw_n)
+        assert torch.equal(db_r, db_n)
+    else:
+        # the ONLY place rounding may move: the two-kernel path rounds
+        # p*(dloss/N) to bf16 before the dW GEMM, the one-pass path rounds
+        # p*(1/N) and applies dloss to the fp32 sums -> one bf16 ulp (2^-8)
+        for r, n in ((dw_r, dw_n), (db_r, db_n)):
+            bound = 2.0 ** -8 * torch.maximum(r.abs(), n.abs())
+            assert ((r - n).abs() <= bound).all(), (r - n).abs().max()
