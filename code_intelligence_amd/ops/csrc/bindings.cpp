@@ -28,7 +28,7 @@ void lstm_seq_forward_gemv_fp8(at::Tensor xp, at::Tensor bias, at::Tensor h0,
 void lstm_seq_backward(at::Tensor dhs, at::Tensor dhT, at::Tensor dcT,
                        at::Tensor gates, at::Tensor hs, at::Tensor cs,
                        at::Tensor c0, at::Tensor w_hh, at::Tensor dgates,
-                       at::Tensor dh0, at::Tensor dc0);
+                       at::Tensor dh0, at::Tensor dc0, bool need_dh0);
 at::Tensor concat_pool(at::Tensor hidden, at::Tensor lengths);
 std::vector<at::Tensor> qrnn_fo_pool_fwd(at::Tensor gates, at::Tensor c0);
 std::vector<at::Tensor> qrnn_fo_pool_bwd(at::Tensor gates, at::Tensor c,
@@ -78,7 +78,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lstm_seq_forward_gemv_fp8", &ci::lstm_seq_forward_gemv_fp8,
         "LSTM sequence forward (fp8-weight GEMV+cell kernel)");
   m.def("lstm_seq_backward", &ci::lstm_seq_backward,
-        "LSTM sequence backward (pointwise + per-step GEMM)");
+        "LSTM sequence backward (pointwise + per-step GEMM)",
+        py::arg("dhs"), py::arg("dhT"), py::arg("dcT"), py::arg("gates"),
+        py::arg("hs"), py::arg("cs"), py::arg("c0"), py::arg("w_hh"),
+        py::arg("dgates"), py::arg("dh0"), py::arg("dc0"),
+        py::arg("need_dh0") = true);
   m.def("concat_pool", &ci::concat_pool, "masked mean/max/last concat pool");
   m.def("qrnn_fo_pool_fwd", &ci::qrnn_fo_pool_fwd,
         "QRNN fo-pool forward scan (activates gates in place)");

@@ -173,15 +173,15 @@ __global__ __launch_bounds__(THREADS) void lstm_cell_fused(
       if (kt + 1 < nk) stage(kt + 1, cur ^ 1);  // flight hides under MFMA
       #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        bf16x8 af[4], bfr[2];
+        bf16x8 af[FM], bfr[FN];
         #pragma unroll
-        for (int f = 0; f < 4; ++f) af[f] = frag(LA(cur), wm + f * 16, ks, lane);
+        for (int f = 0; f < FM; ++f) af[f] = frag(LA(cur), wm + f * 16, ks, lane);
         #pragma unroll
-        for (int f = 0; f < 2; ++f) bfr[f] = frag(LB(cur), wn + f * 16, ks, lane);
+        for (int f = 0; f < FN; ++f) bfr[f] = frag(LB(cur), wn + f * 16, ks, lane);
         #pragma unroll
-        for (int fm = 0; fm < 4; ++fm)
+        for (int fm = 0; fm < FM; ++fm)
           #pragma unroll
-          for (int fn = 0; fn < 2; ++fn)
+          for (int fn = 0; fn < FN; ++fn)
             acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                 af[fm], bfr[fn], acc[fm][fn], 0, 0, 0);
       }
@@ -190,27 +190,34 @@ __global__ __launch_bounds__(THREADS) void lstm_cell_fused(
   } else {
     // 3-stage pipeline: prefetch depth 2 so a tile's glds flight hides
     // under TWO MFMA phases (the 2-stage version stalls ~half the loop on
-    // load latency — PMC r1 'occupancy/latency-bound'). Counted
-    // s_waitcnt vmcnt(12) tolerates the 12 in-flight loads of the two
-    // younger tiles ((BM+BN)/32 = 6 glds per thread per stage).
+    // load latency — PMC r1 'occupancy/latency-bound'). The counted
+    // s_waitcnt tolerates only the loads of the stages YOUNGER than kt:
+    // a stage is (BM+BN)/32 glds per thread and min(2, nk-1-kt) younger
+    // stages are in flight, so the last two iterations (and nk < 3) wait
+    // for fewer outstanding loads. VMEM loads retire in order, so a
+    // register-staged younger tile (fewer loads left) only over-waits.
+    constexpr int PER_STAGE = (BM + BN) / 32;
     stage(0, 0);
     if (nk > 1) stage(1, 1);
     if (nk > 2) stage(2, 2);
     for (int kt = 0; kt < nk; ++kt) {
       const int cur = kt % 3;
-      waitcnt_vm<12>();        // stage(kt) retired; kt+1/kt+2 may be in flight
+      const int younger = nk - 1 - kt;   // stages issued after stage kt
+      if (younger >= 2) waitcnt_vm<2 * PER_STAGE>();
+      else if (younger == 1) waitcnt_vm<PER_STAGE>();
+      else waitcnt_vm<0>();    // stage(kt) retired in every case
       __builtin_amdgcn_s_barrier();
       #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        bf16x8 af[4], bfr[2];
+        bf16x8 af[FM], bfr[FN];
         #pragma unroll
-        for (int f = 0; f < 4; ++f) af[f] = frag(LA(cur), wm + f * 16, ks, lane);
+        for (int f = 0; f < FM; ++f) af[f] = frag(LA(cur), wm + f * 16, ks, lane);
         #pragma unroll
-        for (int f = 0; f < 2; ++f) bfr[f] = frag(LB(cur), wn + f * 16, ks, lane);
+        for (int f = 0; f < FN; ++f) bfr[f] = frag(LB(cur), wn + f * 16, ks, lane);
         #pragma unroll
-        for (int fm = 0; fm < 4; ++fm)
+        for (int fm = 0; fm < FM; ++fm)
           #pragma unroll
-          for (int fn = 0; fn < 2; ++fn)
+          for (int fn = 0; fn < FN; ++fn)
             acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                 af[fm], bfr[fn], acc[fm][fn], 0, 0, 0);
       }
@@ -310,7 +317,7 @@ void lstm_seq_forward_fused(at::Tensor xp, at::Tensor bias, at::Tensor h0,
                             at::Tensor c0, at::Tensor w_hh, at::Tensor hs,
                             at::Tensor cs, at::Tensor gates) {
   CI_CHECK_CUDA(xp); CI_CHECK_CONTIG(xp); CI_CHECK_CONTIG(hs);
-  CI_CHECK_CONTIG(cs); CI_CHECK_CONTIG(gates);
+  CI_CHECK_CONTIG(cs); CI_CHECK_CONTIG(gates); CI_CHECK_CONTIG(c0);
   TORCH_CHECK(xp.scalar_type() == at::ScalarType::BFloat16,
               "fused LSTM cell kernel is bf16; use CI_LSTM_MODE=lib for fp32");
   TORCH_CHECK(w_hh.is_contiguous(), "w_hh must be contiguous");

@@ -225,9 +225,10 @@ void lstm_seq_forward_gemv(at::Tensor xp, at::Tensor bias, at::Tensor h0,
                            at::Tensor c0, at::Tensor w_hh, at::Tensor hs,
                            at::Tensor cs, at::Tensor gates) {
   CI_CHECK_CUDA(xp); CI_CHECK_CONTIG(xp); CI_CHECK_CONTIG(hs);
-  CI_CHECK_CONTIG(cs); CI_CHECK_CONTIG(gates);
+  CI_CHECK_CONTIG(cs); CI_CHECK_CONTIG(gates); CI_CHECK_CONTIG(c0);
   TORCH_CHECK(xp.scalar_type() == at::ScalarType::BFloat16,
               "gemv cell kernel is bf16");
+  TORCH_CHECK(w_hh.is_contiguous(), "w_hh must be contiguous");
   const int T = xp.size(0), B = xp.size(1);
   TORCH_CHECK(B <= 8, "gemv cell kernel is for B <= 8 (got ", B, ")");
   const int H = w_hh.size(1);
@@ -262,7 +263,9 @@ long lstm_seq_forward_gemv_persistent(at::Tensor xp, at::Tensor bias,
                                       at::Tensor ws) {
   CI_CHECK_CUDA(xp); CI_CHECK_CONTIG(xp); CI_CHECK_CONTIG(hs);
   CI_CHECK_CONTIG(cs); CI_CHECK_CONTIG(gates); CI_CHECK_CONTIG(ws);
+  CI_CHECK_CONTIG(c0);
   TORCH_CHECK(xp.scalar_type() == at::ScalarType::BFloat16);
+  TORCH_CHECK(w_hh.is_contiguous(), "w_hh must be contiguous");
   TORCH_CHECK(ws.numel() >= 4 && ws.scalar_type() == at::ScalarType::Int);
   const int T = xp.size(0), B = xp.size(1);
   TORCH_CHECK(B <= 8, "gemv persistent kernel is for B <= 8");
@@ -386,6 +389,7 @@ void lstm_seq_forward_gemv_fp8(at::Tensor xp, at::Tensor bias, at::Tensor h0,
                                at::Tensor hs, at::Tensor cs, at::Tensor gates) {
   CI_CHECK_CUDA(xp); CI_CHECK_CONTIG(xp); CI_CHECK_CONTIG(hs);
   CI_CHECK_CONTIG(cs); CI_CHECK_CONTIG(gates); CI_CHECK_CONTIG(w8);
+  CI_CHECK_CONTIG(c0);
   const int T = xp.size(0), B = xp.size(1);
   TORCH_CHECK(B <= 8, "fp8 gemv kernel is for B <= 8");
   const int H = w8.size(1);

@@ -124,6 +124,7 @@ __global__ void lstm_cell_bwd(
     const float* __restrict__ c_prev, long cp_rs,
     const float* __restrict__ c_t, long ct_rs,
     T* __restrict__ dgates, long dg_rs,
+    float* __restrict__ dgates32,              // optional unrounded copy, (B,4H)
     int B, int H) {
   constexpr int VEC = VECTOR ? 16 / (int)sizeof(T) : 1;
   const int Hv = H / VEC;
@@ -179,6 +180,14 @@ __global__ void lstm_cell_bwd(
     st(dgates + dgo_ + 2 * H, dgg[0]);
     st(dgates + dgo_ + 3 * H, dgo[0]);
   }
+  if (dgates32 != nullptr) {
+    float* d32 = dgates32 + (long)b * 4 * H + j;
+    #pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      d32[e] = dgi[e]; d32[H + e] = dgf[e];
+      d32[2 * H + e] = dgg[e]; d32[3 * H + e] = dgo[e];
+    }
+  }
 }
 
 template <typename ST>
@@ -228,7 +237,7 @@ void lstm_seq_forward_lib(at::Tensor xp, at::Tensor bias, at::Tensor h0,
                           at::Tensor c0, at::Tensor w_hh, at::Tensor hs,
                           at::Tensor cs, at::Tensor gates) {
   CI_CHECK_CUDA(xp); CI_CHECK_CONTIG(xp); CI_CHECK_CONTIG(hs);
-  CI_CHECK_CONTIG(cs); CI_CHECK_CONTIG(gates);
+  CI_CHECK_CONTIG(cs); CI_CHECK_CONTIG(gates); CI_CHECK_CONTIG(c0);
   const int T = xp.size(0), B = xp.size(1);
   const int H = w_hh.size(1);
   auto w_hh_t = w_hh.t();
@@ -258,6 +267,7 @@ void lstm_seq_forward_lib_fp8(at::Tensor xp, at::Tensor bias, at::Tensor h0,
                               at::Tensor hs, at::Tensor cs, at::Tensor gates) {
   CI_CHECK_CUDA(xp); CI_CHECK_CONTIG(xp); CI_CHECK_CONTIG(hs);
   CI_CHECK_CONTIG(cs); CI_CHECK_CONTIG(gates); CI_CHECK_CONTIG(w8);
+  CI_CHECK_CONTIG(c0);
   TORCH_CHECK(xp.scalar_type() == at::ScalarType::BFloat16,
               "fp8 recurrent path is bf16-activation only");
   TORCH_CHECK(w8.scalar_type() == at::ScalarType::Float8_e4m3fn);
@@ -294,12 +304,15 @@ void lstm_seq_forward_lib_fp8(at::Tensor xp, at::Tensor bias, at::Tensor h0,
 void lstm_seq_backward(at::Tensor dhs, at::Tensor dhT, at::Tensor dcT,
                        at::Tensor gates, at::Tensor hs, at::Tensor cs,
                        at::Tensor c0, at::Tensor w_hh, at::Tensor dgates,
-                       at::Tensor dh0, at::Tensor dc0) {
+                       at::Tensor dh0, at::Tensor dc0, bool need_dh0) {
   CI_CHECK_CUDA(dhs); CI_CHECK_CONTIG(dhs); CI_CHECK_CONTIG(dgates);
+  CI_CHECK_CONTIG(c0);
   const int T = dhs.size(0), B = dhs.size(1);
   const int H = w_hh.size(1);
-  auto dc_buf = dcT.clone();                       // (B,H) fp32 running dc
-  auto dh_rec = dhT.contiguous();                  // (B,H) scalar running rec grad
+  auto dc_buf = dcT.clone(at::MemoryFormat::Contiguous);  // (B,H) fp32 running dc
+  // clone, not contiguous(): mm_out below overwrites dh_rec every step and
+  // contiguous() would alias the caller's gradient tensor
+  auto dh_rec = dhT.clone(at::MemoryFormat::Contiguous);  // (B,H) running rec grad
   // one 46 MB transpose buys the NT GEMM layout for all T steps:
   // mm(dgates, w_hh) NN measured 304 TF vs 503 TF as mm(dgates, w_t.t())
   // (scripts/gemm_probe.py on MI355X)
@@ -313,6 +326,15 @@ void lstm_seq_backward(at::Tensor dhs, at::Tensor dhT, at::Tensor dcT,
     constexpr int VEC = 16 / sizeof(scalar_t);
     const bool vec_ok = (H % VEC) == 0;
     const int blocks = ceil_div((long)B * (vec_ok ? H / VEC : H), threads);
+    // dh0 is an fp32 output, so the last step's GEMM must not start from
+    // the bf16-stored dgates (a 2^-9 error per product that shows wherever
+    // the 4H-term sum cancels): step 0 also emits its dgates unrounded and
+    // dh0 = dgates32 @ w_hh runs in fp32. Callers whose h0 needs no
+    // gradient (the trainer detaches carried state) skip that GEMM.
+    const bool lowp = dhs.scalar_type() != at::ScalarType::Float;
+    at::Tensor dg32;
+    if (lowp && need_dh0)
+      dg32 = at::empty({B, 4 * H}, dhs.options().dtype(at::ScalarType::Float));
     for (int t = T - 1; t >= 0; --t) {
       const float* cprev = (t == 0) ? c0.data_ptr<float>()
                                     : cs.data_ptr<float>() + (long)(t - 1) * B * H;
@@ -326,13 +348,18 @@ void lstm_seq_backward(at::Tensor dhs, at::Tensor dhT, at::Tensor dcT,
           cprev, (long)H,
           cs.data_ptr<float>() + (long)t * B * H, (long)H,
           reinterpret_cast<scalar_t*>(dgates.data_ptr()) + (long)t * B * 4 * H, (long)4 * H,
+          (t == 0 && dg32.defined()) ? dg32.data_ptr<float>() : nullptr,
           B, H);
       // dh_{t-1} recurrent contribution: dgates_t @ w_hh (NT layout,
       // contiguous A thanks to time-major dgates)
-      at::mm_out(dh_rec, dgates.select(0, t), w_hh_nt);
+      if (t > 0 || (need_dh0 && !lowp))
+        at::mm_out(dh_rec, dgates.select(0, t), w_hh_nt);
+    }
+    if (need_dh0) {
+      if (lowp) dh0.copy_(at::mm(dg32, w_hh.to(at::ScalarType::Float)));
+      else dh0.copy_(dh_rec);
     }
   });
-  dh0.copy_(dh_rec);
   dc0.copy_(dc_buf);
 }
 

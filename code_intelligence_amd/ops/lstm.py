@@ -145,6 +145,10 @@ class _FusedLSTMFunction(torch.autograd.Function):
         # time-major input; free when x is already a (T,B,·) transpose view
         x_tm = x.transpose(0, 1).contiguous()
         bias = (b_ih + b_hh).to(torch.float32)
+        # the drivers read h0/c0 as dense (B,H) rows: a strided view (e.g. a
+        # column slice of a wider state tensor) is packed once, here
+        h0 = h0.contiguous()
+        c32 = c0.to(torch.float32).contiguous()
         shapes_ok = (dt == torch.bfloat16 and B > 8 and B % 16 == 0
                      and (T * B) % 16 == 0 and In % 16 == 0 and H % 16 == 0)
         fp8 = _lstm_fp8_enabled() and shapes_ok
@@ -170,8 +174,7 @@ class _FusedLSTMFunction(torch.autograd.Function):
             # GEMV+cell kernel replaces hipBLASLt GEMV + pointwise launch
             if os.environ.get("CI_SERVE_FP8W", "0") == "1"                     and not torch.is_grad_enabled():
                 w8, wscale = _fp8_weights(w_hh)
-                lib.lstm_seq_forward_gemv_fp8(xp, bias, h0,
-                                              c0.to(torch.float32), w8,
+                lib.lstm_seq_forward_gemv_fp8(xp, bias, h0, c32, w8,
                                               wscale, hs, cs, gates)
             elif os.environ.get("CI_SERVE_PERSISTENT", "0") == "1" \
                     and not getattr(_FusedLSTMFunction, "_pers_failed", False):
@@ -180,7 +183,6 @@ class _FusedLSTMFunction(torch.autograd.Function):
                 # bails (fail flag) instead of hanging if the grid is
                 # not co-resident; fall back per-step then.
                 ws = torch.zeros(4, dtype=torch.int32, device=x.device)
-                c32 = c0.to(torch.float32)
                 nb = lib.lstm_seq_forward_gemv_persistent(
                     xp, bias, h0, c32, w_hh, hs, cs, gates, ws)
                 if nb == 0 or int(ws[2].item()) != 0:
@@ -191,22 +193,21 @@ class _FusedLSTMFunction(torch.autograd.Function):
                     lib.lstm_seq_forward_gemv(xp, bias, h0, c32,
                                               w_hh, hs, cs, gates)
             else:
-                lib.lstm_seq_forward_gemv(xp, bias, h0, c0.to(torch.float32),
+                lib.lstm_seq_forward_gemv(xp, bias, h0, c32,
                                           w_hh, hs, cs, gates)
         elif dt == torch.bfloat16 and H % 8 == 0 and (
                 mode == "fused"
                 or (mode == "auto" and H >= 2048 and B >= 128)):
             # "auto": fused MFMA cell only where its grid fills the chip
             # (H=2400 layers -> 600 blocks); small layers stay on lib
-            lib.lstm_seq_forward_fused(xp, bias, h0, c0.to(torch.float32), w_hh,
+            lib.lstm_seq_forward_fused(xp, bias, h0, c32, w_hh,
                                        hs, cs, gates)
         elif fp8 and mode == "lib":
             whh8, swh = _q8(lib, w_hh)
-            lib.lstm_seq_forward_lib_fp8(xp, bias, h0.contiguous(),
-                                         c0.to(torch.float32), whh8, swh,
+            lib.lstm_seq_forward_lib_fp8(xp, bias, h0, c32, whh8, swh,
                                          hs, cs, gates)
         else:
-            lib.lstm_seq_forward_lib(xp, bias, h0, c0.to(torch.float32), w_hh,
+            lib.lstm_seq_forward_lib(xp, bias, h0, c32, w_hh,
                                      hs, cs, gates)
         ctx.save_for_backward(x_tm, h0, c0, w_ih, w_hh, gates, hs, cs)
         ctx.direct_params = (w_ih, b_ih, b_hh)  # no other graph consumers
@@ -225,11 +226,16 @@ class _FusedLSTMFunction(torch.autograd.Function):
         dhs_tm = dhs.transpose(0, 1).contiguous()
         dgates = torch.empty(T, B, 4 * H, dtype=dt, device=x_tm.device)
         dh0 = torch.empty(B, H, dtype=torch.float32, device=x_tm.device)
+        # carried state is detached in training: then the step-0 dh GEMM
+        # (fp32, from unrounded dgates) is skipped and no dh0 is returned
+        need_dh0 = ctx.needs_input_grad[1]
         dc0 = torch.empty(B, H, dtype=torch.float32, device=x_tm.device)
         lib.lstm_seq_backward(dhs_tm, dhT.contiguous(),
                               dcT.to(torch.float32).contiguous(),
-                              gates, hs, cs, c0.to(torch.float32), w_hh,
-                              dgates, dh0, dc0)
+                              gates, hs, cs,
+                              c0.to(torch.float32).contiguous(), w_hh,
+                              dgates, dh0, dc0, need_dh0)
+        dh0_out = dh0.to(dt) if need_dh0 else None
         dg2 = dgates.view(T * B, 4 * H)
         dx_tm = torch.mm(dg2, w_ih).view(T, B, In)
         # dW_hh = sum_t h_{t-1}^T dgates_t — time-major slices stay
@@ -253,11 +259,11 @@ class _FusedLSTMFunction(torch.autograd.Function):
                 # clone: assigning the SAME tensor as both .grads would alias
                 # them and double-count on later accumulation micro-steps
                 _accum_grad(pbh, db_s.clone())
-            return (dx_tm.transpose(0, 1), dh0.to(dt), dc0.to(dt),
+            return (dx_tm.transpose(0, 1), dh0_out, dc0.to(dt),
                     None, dw_hh.to(w_hh.dtype), None, None)
         dw_ih = torch.mm(dg2.t(), x_tm.view(T * B, In))
         db = dg2.sum(dim=0).to(dt)
-        return (dx_tm.transpose(0, 1), dh0.to(dt), dc0.to(dt),
+        return (dx_tm.transpose(0, 1), dh0_out, dc0.to(dt),
                 dw_ih.to(w_ih.dtype), dw_hh.to(w_hh.dtype), db, db.clone())
 
 

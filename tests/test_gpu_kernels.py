@@ -19,10 +19,14 @@ def _cpu_lstm_ref(x, h0, c0, w_ih, w_hh, b_ih, b_hh):
 
 @pytest.mark.parametrize("mode", ["lib", "fused"])
 @pytest.mark.parametrize("shape", [(8, 5, 64, 96), (130, 3, 128, 256)])
-def test_lstm_forward_matches_cpu_fp32(mode, shape):
+def test_lstm_forward_matches_cpu_fp32(monkeypatch, mode, shape):
+    # "fused" = CI_LSTM_MODE=fused in bf16. Only the B=130 shape reaches the
+    # MFMA kernel: bf16 with B <= 8 dispatches to the GEMV cell kernel, so
+    # (8,5,64,96)[fused] is a GEMV test. The MFMA kernel's own small-shape
+    # tests are in test_gpu_lstm.py.
     torch.manual_seed(0)
     B, T, In, H = shape
-    os.environ["CI_LSTM_MODE"] = mode
+    monkeypatch.setenv("CI_LSTM_MODE", mode)
     x32 = torch.randn(B, T, In)
     w_ih = torch.randn(4 * H, In) * 0.1
     w_hh = torch.randn(4 * H, H) * 0.1
@@ -44,10 +48,10 @@ def test_lstm_forward_matches_cpu_fp32(mode, shape):
 
 
 @pytest.mark.parametrize("mode", ["lib", "fused"])
-def test_lstm_backward_matches_cpu_fp32(mode):
+def test_lstm_backward_matches_cpu_fp32(monkeypatch, mode):
     torch.manual_seed(1)
     B, T, In, H = 16, 4, 32, 48
-    os.environ["CI_LSTM_MODE"] = mode
+    monkeypatch.setenv("CI_LSTM_MODE", mode)
     dt = torch.bfloat16 if mode == "fused" else torch.float32
 
     def run(device, dtype):
@@ -147,10 +151,12 @@ def test_native_extension_is_loaded():
 
 
 @pytest.mark.parametrize("mode", ["lib", "fused"])
-def test_lstm_tiny_shapes(mode):
-    """Edge grids: B=1 (heavy M-tail), T=1, odd batch."""
+def test_lstm_tiny_shapes(monkeypatch, mode):
+    """Edge grids: B=1, T=1, odd batch. All three have B <= 8, so the
+    "fused" (bf16) variant runs the GEMV cell kernel, not the MFMA one;
+    "lib" runs the fp32 pointwise path."""
     from code_intelligence_amd.ops.lstm import lstm_forward, _cpu_lstm_loop
-    os.environ["CI_LSTM_MODE"] = mode
+    monkeypatch.setenv("CI_LSTM_MODE", mode)
     for B, T, In, H in [(1, 3, 16, 32), (3, 1, 32, 64), (5, 2, 24, 40)]:
         torch.manual_seed(B * 100 + T)
         x = torch.randn(B, T, In)
@@ -181,7 +187,7 @@ def test_concat_pool_length_one_and_full():
     assert torch.allclose(got, ref, atol=1e-5)
 
 
-def test_ce_chunk_boundary():
+def test_ce_chunk_boundary(monkeypatch):
     """N not divisible by CHUNK and N < CHUNK both exercised."""
     import code_intelligence_amd.ops.crossentropy as ce
     from code_intelligence_amd.ops.crossentropy import tied_decoder_ce
@@ -189,7 +195,7 @@ def test_ce_chunk_boundary():
     old = ce._FusedCEFunction.CHUNK
     try:
         ce._FusedCEFunction.CHUNK = 7
-        os.environ["CI_CE_CHUNK"] = "7"
+        monkeypatch.setenv("CI_CE_CHUNK", "7")
         torch.manual_seed(0)
         h = torch.randn(23, 16, device=DEV)
         w = torch.randn(50, 16, device=DEV) * 0.3
@@ -199,7 +205,6 @@ def test_ce_chunk_boundary():
         assert abs(float(loss) - float(ref)) < 1e-4
     finally:
         ce._FusedCEFunction.CHUNK = old
-        os.environ.pop("CI_CE_CHUNK", None)
 
 
 @pytest.mark.parametrize("H", [96, 10])  # vector path / scalar-tail path
@@ -375,7 +380,7 @@ def test_weightdrop_lstm_train_step_runs_with_kernels():
 # ---- deployed-shape correctness ---------------
 
 @pytest.mark.timeout(600)
-def test_lstm_deployed_shape_fused_vs_lib_vs_cpu_spot():
+def test_lstm_deployed_shape_fused_vs_lib_vs_cpu_spot(monkeypatch):
     """H=2400, B=512, T=2 (the bench kernel grid incl. edge tiles): fused
     and lib paths must agree with each other everywhere and with a CPU
     fp32 reference on spot rows."""
@@ -394,7 +399,7 @@ def test_lstm_deployed_shape_fused_vs_lib_vs_cpu_spot():
 
     outs = {}
     for mode in ("lib", "fused"):
-        os.environ["CI_LSTM_MODE"] = mode
+        monkeypatch.setenv("CI_LSTM_MODE", mode)
         args = [x32.to(DEV, torch.bfloat16),
                 torch.zeros(B, H, device=DEV, dtype=torch.bfloat16),
                 torch.zeros(B, H, device=DEV, dtype=torch.bfloat16),
@@ -402,7 +407,6 @@ def test_lstm_deployed_shape_fused_vs_lib_vs_cpu_spot():
                 b_ih.to(DEV, torch.bfloat16), b_hh.to(DEV, torch.bfloat16)]
         out, (hT, cT) = lstm_forward(*args)
         outs[mode] = (out.float().cpu(), hT.float().cpu())
-    os.environ.pop("CI_LSTM_MODE", None)
     # fused vs lib: same bf16 inputs, both fp32-accumulated -> tight
     assert torch.allclose(outs["fused"][0], outs["lib"][0], atol=0.02), \
         (outs["fused"][0] - outs["lib"][0]).abs().max()
@@ -415,7 +419,7 @@ def test_lstm_deployed_shape_fused_vs_lib_vs_cpu_spot():
 
 # ---- fp8 CE GEMM path (CI_CE_FP8R, round 2) -------------------------------
 
-def _ce_both_paths(N, H, V, seed=11):
+def _ce_both_paths(monkeypatch, N, H, V, seed=11):
     from code_intelligence_amd.ops.crossentropy import tied_decoder_ce
     torch.manual_seed(seed)
     h0 = torch.randn(N, H) * 0.5
@@ -424,7 +428,7 @@ def _ce_both_paths(N, H, V, seed=11):
     t0 = torch.randint(0, V, (N,))
     res = {}
     for mode in ("bf16", "fp8r"):
-        os.environ["CI_CE_FP8R"] = "1" if mode == "fp8r" else "0"
+        monkeypatch.setenv("CI_CE_FP8R", "1" if mode == "fp8r" else "0")
         h = h0.to(DEV, torch.bfloat16).requires_grad_(True)
         w = w0.to(DEV, torch.bfloat16).requires_grad_(True)
         b = b0.to(DEV, torch.bfloat16).requires_grad_(True)
@@ -432,15 +436,15 @@ def _ce_both_paths(N, H, V, seed=11):
         loss.backward()
         res[mode] = (float(loss), h.grad.float().cpu(), w.grad.float().cpu(),
                      b.grad.float().cpu())
-    os.environ.pop("CI_CE_FP8R", None)
+    monkeypatch.delenv("CI_CE_FP8R")
     return res
 
 
 @pytest.mark.timeout(300)
-def test_ce_fp8_resident_close_to_bf16():
+def test_ce_fp8_resident_close_to_bf16(monkeypatch):
     """fp8-input CE GEMMs + fp8 dh: loss within ~2% of the bf16 path and
     gradients directionally identical (cosine > 0.98)."""
-    res = _ce_both_paths(N=2048, H=160, V=4096)
+    res = _ce_both_paths(monkeypatch, N=2048, H=160, V=4096)
     lb, hb, wb, bb = res["bf16"]
     lf, hf, wf, bf_ = res["fp8r"]
     assert abs(lf - lb) / abs(lb) < 0.02, (lf, lb)
@@ -454,14 +458,11 @@ def test_ce_fp8_resident_close_to_bf16():
 
 
 @pytest.mark.timeout(300)
-def test_ce_fp8_resident_tail_chunk():
+def test_ce_fp8_resident_tail_chunk(monkeypatch):
     """N not a multiple of 16 exercises the bf16-GEMM tail fallback for
     both forward quantize-store and backward dh."""
-    os.environ["CI_CE_CHUNK"] = "64"
-    try:
-        res = _ce_both_paths(N=72 + 9, H=160, V=4096, seed=12)
-    finally:
-        os.environ.pop("CI_CE_CHUNK", None)
+    monkeypatch.setenv("CI_CE_CHUNK", "64")
+    res = _ce_both_paths(monkeypatch, N=72 + 9, H=160, V=4096, seed=12)
     lb, hb, *_ = res["bf16"]
     lf, hf, *_ = res["fp8r"]
     assert abs(lf - lb) / abs(lb) < 0.03
@@ -569,7 +570,7 @@ def test_artar_engages_on_trainer_layout():
 # ---- fp8 LSTM GEMM path (CI_LSTM_FP8, round 2) ----------------------------
 
 @pytest.mark.timeout(300)
-def test_lstm_fp8_close_to_bf16():
+def test_lstm_fp8_close_to_bf16(monkeypatch):
     """fp8 input-projection + fp8 recurrent GEMM (fixed 1/448 h scale):
     outputs within e4m3 tolerance of the bf16 lib path, grads
     directionally identical."""
@@ -578,7 +579,7 @@ def test_lstm_fp8_close_to_bf16():
     B, T, In, H = 32, 12, 64, 96
 
     def run(fp8):
-        os.environ["CI_LSTM_FP8"] = "1" if fp8 else "0"
+        monkeypatch.setenv("CI_LSTM_FP8", "1" if fp8 else "0")
         torch.manual_seed(22)
         x = (torch.randn(B, T, In) * 0.5).to(DEV, torch.bfloat16) \
             .requires_grad_(True)
@@ -594,11 +595,8 @@ def test_lstm_fp8_close_to_bf16():
         return (out.detach().float().cpu(), x.grad.float().cpu(),
                 w_hh.grad.float().cpu())
 
-    try:
-        out_b, gx_b, gw_b = run(False)
-        out_f, gx_f, gw_f = run(True)
-    finally:
-        os.environ.pop("CI_LSTM_FP8", None)
+    out_b, gx_b, gw_b = run(False)
+    out_f, gx_f, gw_f = run(True)
     # forward: fp8 quantization noise bounded
     assert torch.allclose(out_f, out_b, atol=0.06), \
         (out_f - out_b).abs().max()
@@ -681,11 +679,11 @@ def test_persistent_gemv_serve_wrapper_path():
 
 
 @pytest.mark.timeout(300)
-def test_ce_fp8_extreme_logits_no_overflow():
+def test_ce_fp8_extreme_logits_no_overflow(monkeypatch):
     """Large-magnitude hidden states / weights (|logits| in the hundreds)
     must not overflow the fp8 CE path: per-tensor input scales keep the
     GEMM inputs in range and the loss stays finite and close to bf16."""
-    res = _ce_both_paths(N=512, H=160, V=2048, seed=41)
+    res = _ce_both_paths(monkeypatch, N=512, H=160, V=2048, seed=41)
     # scale inputs up via a fresh run with big tensors
     from code_intelligence_amd.ops.crossentropy import tied_decoder_ce
     torch.manual_seed(42)
@@ -693,12 +691,9 @@ def test_ce_fp8_extreme_logits_no_overflow():
     w = (torch.randn(2048, 160) * 2).to(DEV, torch.bfloat16).requires_grad_(True)
     b = (torch.randn(2048) * 4).to(DEV, torch.bfloat16).requires_grad_(True)
     t = torch.randint(0, 2048, (512,), device=DEV)
-    os.environ["CI_CE_FP8R"] = "1"
-    try:
-        loss = tied_decoder_ce(h, w, b, t)
-        loss.backward()
-    finally:
-        os.environ.pop("CI_CE_FP8R", None)
+    monkeypatch.setenv("CI_CE_FP8R", "1")
+    loss = tied_decoder_ce(h, w, b, t)
+    loss.backward()
     assert torch.isfinite(loss), loss
     for g in (h.grad, w.grad, b.grad):
         assert torch.isfinite(g.float()).all()
@@ -706,11 +701,8 @@ def test_ce_fp8_extreme_logits_no_overflow():
     h2 = h.detach().clone().requires_grad_(True)
     w2 = w.detach().clone().requires_grad_(True)
     b2 = b.detach().clone().requires_grad_(True)
-    os.environ["CI_CE_FP8R"] = "0"
-    try:
-        ref = tied_decoder_ce(h2, w2, b2, t)
-    finally:
-        os.environ.pop("CI_CE_FP8R", None)
+    monkeypatch.setenv("CI_CE_FP8R", "0")
+    ref = tied_decoder_ce(h2, w2, b2, t)
     assert abs(float(loss) - float(ref)) / max(abs(float(ref)), 1e-6) < 0.1
 
 

@@ -1,0 +1,365 @@
+"""LSTM HIP kernels vs fp64 references (tests/lstm_ref.py): carried state,
+state gradients and tile edges, driver by driver.
+
+Forward bounds are derived per case, not fixed: with
+E = max|ref_model - ref_exact| (the error the driver's own storage
+roundings cause, computed on the CPU), a kernel must stay within
+K*E + 2^-9 of ref_exact for bf16 hs/gates and K*E + 1e-5 for fp32 cs, K = 2
+(lstm_ref.K_FACTOR); the fp32 driver keeps the suite's 2e-4. The CPU test
+test_lstm_ref.py::test_bounds_catch_permutation_errors shows every bound is
+at least 2x below what a swapped gate pair or a hidden index off by one
+would cause.
+
+Measured on MI355X, worst err/allowed over each driver's cases (K = 2):
+  driver (cases)                          hs     cs     gates
+  lstm_seq_forward_lib fp32 (2e-4 flat)   3e-4   4e-4   4e-4
+  lstm_seq_forward_lib bf16               0.34   0.50   0.39
+  lstm_seq_forward_fused, all 4 variants  0.35   0.50   0.41
+  lstm_seq_forward_gemv                   0.33   0.50   0.39
+  lstm_seq_forward_gemv_persistent        0.33   0.50   0.39
+  lstm_seq_forward_gemv_fp8               0.49   0.50   0.54
+  lstm_seq_forward_lib_fp8                0.49   0.50   0.50
+The four fused variants (128x64 / 64x64 tile, 2- / 3-stage) give identical
+figures. A ratio of 0.5 means the kernel sits as far from ref_exact as
+ref_model does, i.e. its only error is the modelled storage rounding; no
+driver needed K > 2.
+
+Backward, T = 1 (err/allowed, worst element): dgates bf16 0.98, fp32 0.03;
+dc0 0.54; dh0 0.004 (bf16), 0.05 (fp32).
+"""
+import pytest
+import torch
+
+import lstm_ref as R
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+BF16, F32 = torch.bfloat16, torch.float32
+
+_ENV = ("CI_LSTM_MODE", "CI_FUSED_TILE", "CI_FUSED_PIPE", "CI_SERVE_FP8W",
+        "CI_SERVE_PERSISTENT", "CI_LSTM_FP8", "CI_SIDE_DW")
+
+
+@pytest.fixture(autouse=True)
+def _clean_env(monkeypatch):
+    """Every test starts from the default dispatch; whatever a test sets
+    through monkeypatch is undone when it ends."""
+    for k in _ENV:
+        monkeypatch.delenv(k, raising=False)
+
+
+def _lib():
+    from code_intelligence_amd.ops import extension as ext
+    return ext.require()
+
+
+def _nan(*shape, dtype):
+    # NaN-filled outputs: an element the kernel never writes fails the bound
+    return torch.full(shape, float("nan"), dtype=dtype, device=DEV)
+
+
+# ---- 2. forward, driver by driver, through lib.* --------------------------
+
+def _run_driver(driver, inp):
+    lib = _lib()
+    from code_intelligence_amd.ops import lstm as ops_lstm
+    dt = R.driver_dtype(driver)
+    T, B, H4 = inp["xp"].shape
+    H = H4 // 4
+    xp, bias, h0, c0, w = (inp[k].to(DEV) for k in
+                           ("xp", "bias", "h0", "c0", "w_hh"))
+    hs = _nan(T, B, H, dtype=dt)
+    cs = _nan(T, B, H, dtype=F32)
+    gates = _nan(T, B, 4 * H, dtype=dt)
+    if driver in ("lib_fp32", "lib_bf16"):
+        lib.lstm_seq_forward_lib(xp, bias, h0, c0, w, hs, cs, gates)
+    elif driver == "fused":
+        lib.lstm_seq_forward_fused(xp, bias, h0, c0, w, hs, cs, gates)
+    elif driver == "gemv":
+        lib.lstm_seq_forward_gemv(xp, bias, h0, c0, w, hs, cs, gates)
+    elif driver == "gemv_persistent":
+        ws = torch.zeros(4, dtype=torch.int32, device=DEV)
+        nb = lib.lstm_seq_forward_gemv_persistent(xp, bias, h0, c0, w,
+                                                  hs, cs, gates, ws)
+        torch.cuda.synchronize()
+        assert nb > 0, "persistent grid unavailable"
+        assert int(ws[2]) == 0, "grid barrier bailed"
+    elif driver == "gemv_fp8":
+        w8, wscale = ops_lstm._fp8_weights(w)
+        lib.lstm_seq_forward_gemv_fp8(xp, bias, h0, c0, w8, wscale,
+                                      hs, cs, gates)
+    elif driver == "lib_fp8":
+        w8, swh = ops_lstm._q8(lib, w)
+        lib.lstm_seq_forward_lib_fp8(xp, bias, h0, c0, w8, swh,
+                                     hs, cs, gates)
+    else:
+        raise AssertionError(driver)
+    torch.cuda.synchronize()
+    return {"hs": hs, "cs": cs, "gates": gates}
+
+
+def _check_forward(driver, B, H, T, tag=""):
+    case = R.forward_case(driver, B, H, T)
+    got = _run_driver(driver, case["inp"])
+    errs = {}
+    for k in ("hs", "cs", "gates"):
+        errs[k] = float((got[k].double().cpu() - case["exact"][k]).abs().max())
+        print(f"RATIO {driver}{tag} B={B} H={H} T={T} {k}: "
+              f"err={errs[k]:.3e} allowed={case['allowed'][k]:.3e} "
+              f"ratio={errs[k] / case['allowed'][k]:.3f}")
+    for k in errs:
+        assert errs[k] <= case["allowed"][k], \
+            (driver, tag, B, H, T, k, errs[k], case["allowed"][k])
+        # the bound is only worth something if a permutation would break it
+        assert case["moved"][k] > case["allowed"][k], (k, case["moved"][k])
+
+
+def _cases(driver):
+    return [(B, H, T) for (B, H) in R.FORWARD_SHAPES[driver]
+            for T in R.FORWARD_T]
+
+
+@pytest.mark.parametrize("B,H,T", _cases("lib_fp32"))
+def test_forward_lib_fp32(B, H, T):
+    """(3,8) vector only; (5,6) vector + scalar tail; (2,3) tail only."""
+    _check_forward("lib_fp32", B, H, T)
+
+
+@pytest.mark.parametrize("B,H,T", _cases("lib_bf16"))
+def test_forward_lib_bf16(B, H, T):
+    """The default training path. (5,20) and (2,5) run
+    lstm_cell_fwd_tail<bf16>; (67,8) leaves the last 64-thread block
+    partly idle."""
+    _check_forward("lib_bf16", B, H, T)
+
+
+@pytest.mark.parametrize("pipe", [None, "3"])
+@pytest.mark.parametrize("tile", [None, "64x64"])
+@pytest.mark.parametrize("B,H,T", _cases("fused"))
+def test_forward_fused_mfma(monkeypatch, B, H, T, tile, pipe):
+    """The MFMA cell kernel itself (not the GEMV the op picks for B <= 8).
+    (16,8): one block, K < 64, N below the tile. (128,64): all interior,
+    nk = 1, fewer than 8 blocks in the XCD remap. (130,72): M tail, N tail,
+    10 blocks, K tail so interior blocks stage tile 0 by glds and tile 1 by
+    registers. (128,96): interior rows with a K tail."""
+    if tile:
+        monkeypatch.setenv("CI_FUSED_TILE", tile)
+    if pipe:
+        monkeypatch.setenv("CI_FUSED_PIPE", pipe)
+    _check_forward("fused", B, H, T, tag=f"[{tile or '128x64'},p{pipe or 2}]")
+
+
+@pytest.mark.parametrize("B,H,T", _cases("gemv"))
+def test_forward_gemv(B, H, T):
+    """H=50: 6 vectors + scalar tail; H=520: a full 512-wide sweep + 1."""
+    _check_forward("gemv", B, H, T)
+
+
+@pytest.mark.parametrize("B,H,T", _cases("gemv_persistent"))
+def test_forward_gemv_persistent(B, H, T):
+    _check_forward("gemv_persistent", B, H, T)
+
+
+@pytest.mark.parametrize("B,H,T", _cases("gemv_fp8"))
+def test_forward_gemv_fp8(B, H, T):
+    """H=50: 3 vectors + scalar tail; H=1040: a full 1024-wide sweep + 1."""
+    _check_forward("gemv_fp8", B, H, T)
+
+
+@pytest.mark.parametrize("B,H,T", _cases("lib_fp8"))
+def test_forward_lib_fp8(B, H, T):
+    """Includes the fixed-scale quantize_e4m3(h0) of a non-zero h0."""
+    _check_forward("lib_fp8", B, H, T)
+
+
+# ---- 3. backward kernel direct, T = 1 -------------------------------------
+
+_BWD_CASES = [("lib_fp32", 3, 8), ("lib_fp32", 5, 6),
+              ("lib_bf16", 3, 24), ("lib_bf16", 5, 20), ("lib_bf16", 67, 8)]
+_bwd_cache = {}
+
+
+def _run_backward_cell(driver, B, H):
+    """lstm_seq_backward on one cell whose saves come from ref_model;
+    returns kernel outputs, the closed-form fp64 reference on the same
+    rounded inputs, and the gradient tensors before/after. Run once per
+    case and shared."""
+    key = (driver, B, H)
+    if key in _bwd_cache:
+        return _bwd_cache[key]
+    dt = R.driver_dtype(driver)
+    inp = R.draw_inputs(driver, B, H, 1, seed=3)
+    hs, cs, gates = R.ref_model(inp["xp"].transpose(0, 1), inp["h0"],
+                                inp["c0"], None, inp["w_hh"], inp["bias"],
+                                torch.zeros(4 * H), driver)
+    hs, gates, cs = hs.to(dt), gates.to(dt), cs.to(F32)
+    g = torch.Generator().manual_seed(99 + B + H)
+    dhs = torch.randn(1, B, H, generator=g).to(dt)
+    dhT = torch.randn(B, H, generator=g).to(dt)
+    dcT = torch.randn(B, H, generator=g)
+    c0 = inp["c0"]
+    ref = R.cell_backward_exact(dhs[0], dhT, dcT, gates[0], c0, cs[0],
+                                inp["w_hh"])
+    d = lambda t: t.to(DEV)
+    dhT_d, dcT_d = d(dhT), d(dcT)
+    dgates = _nan(1, B, 4 * H, dtype=dt)
+    dh0 = _nan(B, H, dtype=F32)
+    dc0 = _nan(B, H, dtype=F32)
+    _lib().lstm_seq_backward(d(dhs), dhT_d, dcT_d, d(gates), d(hs), d(cs),
+                             d(c0), d(inp["w_hh"]), dgates, dh0, dc0)
+    torch.cuda.synchronize()
+    out = dict(dgates=dgates[0].double().cpu(), dh0=dh0.double().cpu(),
+               dc0=dc0.double().cpu(), ref=ref,
+               dhT=(dhT, dhT_d.cpu()), dcT=(dcT, dcT_d.cpu()))
+    _bwd_cache[key] = out
+    return out
+
+
+def _rel_ok(name, got, ref, rtol, atol):
+    err = (got - ref).abs()
+    lim = rtol * ref.abs() + atol
+    worst = float((err / lim.clamp_min(1e-300)).max())
+    print(f"BWD {name}: max err/allowed = {worst:.3f}, "
+          f"violations = {int((err > lim).sum())}/{err.numel()}")
+    assert bool((err <= lim).all()), (name, worst)
+
+
+@pytest.mark.parametrize("driver,B,H", _BWD_CASES)
+def test_backward_cell_dgates_dc0(driver, B, H):
+    """With T = 1 the only error is the output rounding: one bf16 ulp for
+    bf16 dgates (2^-8 |ref| + 1e-6), and purely relative 1e-5, no absolute
+    floor, for the fp32 values (fp32 dgates, dc0 in both types): they are
+    pointwise products, so nothing cancels.
+    (5,20) bf16 takes the scalar kernel lstm_cell_bwd<bf16,false>."""
+    r = _run_backward_cell(driver, B, H)
+    rtol, atol = (1e-5, 0.0) if driver == "lib_fp32" else (2.0 ** -8, 1e-6)
+    _rel_ok(f"{driver} ({B},{H}) dgates", r["dgates"], r["ref"][0], rtol, atol)
+    _rel_ok(f"{driver} ({B},{H}) dc0", r["dc0"], r["ref"][2], 1e-5, 0.0)
+
+
+@pytest.mark.parametrize("driver,B,H", _BWD_CASES)
+def test_backward_cell_dh0(driver, B, H):
+    """dh0 = dgates @ w_hh against the closed form, with the elementwise
+    bound the dgates get: |err| <= 2^-8 |ref| + 1e-6 (bf16), 1e-5 |ref| +
+    1e-6 (fp32). A GEMM over the bf16-STORED dgates cannot meet it (each of
+    the 4H products carries a 2^-9 input error; an ideal single-rounding
+    model of that scheme misses the bound 12-170x on these cases wherever
+    the sum cancels), so step 0 hands the GEMM its dgates unrounded and
+    dh0, an fp32 output, is computed in fp32.
+
+    The fp32 case keeps the 1e-6 floor that the bf16 bound has: dh0 is a
+    sum of 4H products that can cancel, and an fp32 GEMM's error
+    (~4H * 2^-24 * |dgates||w|, about 2e-6 here) does not shrink with
+    |ref|. Plain fp32 arithmetic on the CPU is at 3.1x a floorless 1e-5
+    relative bound on the (3,8) case and at 0.04x with the floor."""
+    r = _run_backward_cell(driver, B, H)
+    rtol = 1e-5 if driver == "lib_fp32" else 2.0 ** -8
+    _rel_ok(f"{driver} ({B},{H}) dh0", r["dh0"], r["ref"][1], rtol, 1e-6)
+
+
+@pytest.mark.parametrize("driver,B,H", _BWD_CASES)
+def test_backward_cell_keeps_callers_gradients(driver, B, H):
+    """dhT and dcT are inputs: bit-unchanged after the call."""
+    r = _run_backward_cell(driver, B, H)
+    assert torch.equal(*r["dhT"]), "lstm_seq_backward overwrote dhT"
+    assert torch.equal(*r["dcT"]), "lstm_seq_backward overwrote dcT"
+
+
+# ---- 4. through lstm_forward and autograd ---------------------------------
+
+_AG_CASES = [  # id, CI_LSTM_MODE, dtype, (B, In, H)
+    ("lib_fp32", "lib", F32, (5, 8, 6)),
+    ("lib_bf16", "lib", BF16, (16, 16, 24)),
+    ("fused_bf16", "fused", BF16, (16, 16, 24)),
+    # B <= 8 in bf16 dispatches to the GEMV forward; H % 8 != 0 sends its
+    # saved gates through the scalar bf16 backward kernel
+    ("gemv_bf16", "lib", BF16, (4, 16, 20)),
+]
+_NAMES = ("x", "h0", "c0", "w_ih", "w_hh", "b_ih", "b_hh")
+
+
+def _ag_inputs(dt, B, T, In, H):
+    g = torch.Generator().manual_seed(17 * B + 3 * T + In + H)
+    r = lambda s, *shape: (s * torch.randn(*shape, generator=g)).to(dt)
+    w_scale = 0.3
+    args = dict(x=r(0.5, B, T, In),
+                h0=r(0.5, B, H).clamp(-0.98, 0.98), c0=r(0.5, B, H),
+                w_ih=r(w_scale, 4 * H, In), w_hh=r(w_scale, 4 * H, H),
+                b_ih=r(0.1, 4 * H), b_hh=r(0.1, 4 * H))
+    grads = dict(out=r(1.0, B, T, H), hT=r(1.0, B, H), cT=r(1.0, B, H))
+    return args, grads
+
+
+def _run_op(args, grads, strided_state=False):
+    from code_intelligence_amd.ops.lstm import lstm_forward
+    leaf = {k: v.to(DEV).requires_grad_(True) for k, v in args.items()}
+    if strided_state:
+        # h0/c0 as column slices of a (B, 2H) tensor: row stride 2H
+        for k in ("h0", "c0"):
+            wide = torch.cat([args[k], args[k].flip(1)], dim=1).to(DEV)
+            leaf[k] = wide[:, :args[k].shape[1]].requires_grad_(True)
+            assert not leaf[k].is_contiguous()
+    gd = {k: v.to(DEV) for k, v in grads.items()}
+    out, (hT, cT) = lstm_forward(*(leaf[k] for k in _NAMES))
+    torch.autograd.backward([out, hT, cT], [gd["out"], gd["hT"], gd["cT"]])
+    torch.cuda.synchronize()
+    res = {"out": out.detach(), "hT": hT.detach(), "cT": cT.detach()}
+    res.update({"d" + k: leaf[k].grad for k in _NAMES})
+    return {k: v.cpu() for k, v in res.items()}, \
+        {k: v.cpu() for k, v in gd.items()}
+
+
+@pytest.mark.parametrize("T", [3, 1])
+@pytest.mark.parametrize("case", _AG_CASES, ids=[c[0] for c in _AG_CASES])
+def test_autograd_all_grads_with_carried_state(monkeypatch, case, T):
+    """Non-zero h0/c0 that require grad, and a loss that depends on out, hT
+    and cT: all seven gradients and the three outputs vs fp64 autograd
+    through ref_exact. Metric and numbers are those of
+    test_lstm_backward_matches_cpu_fp32."""
+    _, mode, dt, (B, In, H) = case
+    monkeypatch.setenv("CI_LSTM_MODE", mode)
+    args, grads = _ag_inputs(dt, B, T, In, H)
+    got, g_after = _run_op(args, grads)
+
+    leaf = {k: v.double().requires_grad_(True) for k, v in args.items()}
+    hs, cs, _ = R.ref_exact(*(leaf[k] for k in _NAMES))
+    torch.autograd.backward(
+        [hs.transpose(0, 1), hs[-1], cs[-1]],
+        [grads[k].double() for k in ("out", "hT", "cT")])
+    want = {"out": hs.transpose(0, 1).detach(), "hT": hs[-1].detach(),
+            "cT": cs[-1].detach()}
+    want.update({"d" + k: leaf[k].grad for k in _NAMES})
+
+    tol = 0.05 if dt == BF16 else 1e-3
+    for k in want:
+        r, g = want[k], got[k].double()
+        assert g.shape == r.shape, (k, g.shape, r.shape)
+        rel = float((r - g).abs().max() / r.abs().max().clamp_min(1e-6))
+        print(f"AG {case[0]} T={T} {k}: rel={rel:.3e} (tol {tol})")
+    for k in want:
+        r, g = want[k], got[k].double()
+        rel = float((r - g).abs().max() / r.abs().max().clamp_min(1e-6))
+        assert rel < tol, (case[0], T, k, rel)
+    # the incoming gradients belong to the caller (defect: dhT was used as
+    # the running dh buffer)
+    for k in ("hT", "cT", "out"):
+        assert torch.equal(g_after[k], grads[k]), f"g_{k} was overwritten"
+
+
+@pytest.mark.parametrize("case", _AG_CASES, ids=[c[0] for c in _AG_CASES])
+def test_strided_state_equals_contiguous(monkeypatch, case):
+    """h0/c0 passed as column slices of a (B, 2H) tensor give bit-identical
+    outputs and gradients to their contiguous copies. Before h0/c0 were
+    packed in ops/lstm.py only the fp32 case could go wrong: there
+    c0.to(float32) is the strided view itself, read with row stride H. In
+    bf16 the cast already packs a non-dense c0, and the fused and GEMV
+    drivers packed h0; those cases guard the contract, not an old bug."""
+    _, mode, dt, (B, In, H) = case
+    monkeypatch.setenv("CI_LSTM_MODE", mode)
+    args, grads = _ag_inputs(dt, B, 3, In, H)
+    a, _ = _run_op(args, grads)
+    b, _ = _run_op(args, grads, strided_state=True)
+    for k in a:
+        assert torch.equal(a[k], b[k]), \
+            (k, (a[k].float() - b[k].float()).abs().max())
