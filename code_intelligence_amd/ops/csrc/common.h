@@ -39,9 +39,11 @@ template <typename T>
 static __device__ __forceinline__ void st(T* p, float v) { Cvt<T>::store(p, v); }
 
 // ---- 16-B vectorized load/store of VEC scalars as fp32 lanes -------------
-// (G13: scalar bf16 loads cost ~2x; VEC = 16/sizeof(T))
+// (G13: scalar bf16 loads cost ~2x; VEC = 16/sizeof(T)). VEC = 1 is the
+// plain scalar access, so one kernel body serves vector and tail columns.
 template <typename T, int VEC>
 static __device__ __forceinline__ void ldv(const T* p, float* out) {
+  if constexpr (VEC == 1) { out[0] = ld(p); return; }
   T buf[VEC];
   *reinterpret_cast<int4*>(buf) = *reinterpret_cast<const int4*>(p);
   #pragma unroll
@@ -50,6 +52,7 @@ static __device__ __forceinline__ void ldv(const T* p, float* out) {
 
 template <typename T, int VEC>
 static __device__ __forceinline__ void stv(T* p, const float* v) {
+  if constexpr (VEC == 1) { st(p, v[0]); return; }
   T buf[VEC];
   #pragma unroll
   for (int e = 0; e < VEC; ++e) st(buf + e, v[e]);
@@ -58,6 +61,7 @@ static __device__ __forceinline__ void stv(T* p, const float* v) {
 
 template <int VEC>
 static __device__ __forceinline__ void ldv_f32(const float* p, float* out) {
+  if constexpr (VEC == 1) { out[0] = p[0]; return; }
   #pragma unroll
   for (int e = 0; e < VEC; e += 4)
     *reinterpret_cast<float4*>(out + e) = *reinterpret_cast<const float4*>(p + e);
@@ -65,6 +69,7 @@ static __device__ __forceinline__ void ldv_f32(const float* p, float* out) {
 
 template <int VEC>
 static __device__ __forceinline__ void stv_f32(float* p, const float* v) {
+  if constexpr (VEC == 1) { p[0] = v[0]; return; }
   #pragma unroll
   for (int e = 0; e < VEC; e += 4)
     *reinterpret_cast<float4*>(p + e) = *reinterpret_cast<const float4*>(v + e);

@@ -26,7 +26,7 @@
 //
 // Weight-drop (K3) masks are applied by the caller (masked W arrives
 // here), matching fastai WeightDropout (train.py:70).
-#include "common.h"
+#include "lstm_cell.h"
 
 namespace ci {
 
@@ -254,21 +254,11 @@ __global__ __launch_bounds__(THREADS) void lstm_cell_fused(
     const int j = jt + jj;
     if (b >= B || j >= H) continue;
     const float* qp = pre + br * PRS + jj * 4;
-    const long xo = (long)b * xp_rs + j;
-    float gi = qp[0] + __bfloat162float(xp[xo]) + bias[j];
-    float gf = qp[1] + __bfloat162float(xp[xo + H]) + bias[j + H];
-    float gg = qp[2] + __bfloat162float(xp[xo + 2 * H]) + bias[j + 2 * H];
-    float go = qp[3] + __bfloat162float(xp[xo + 3 * H]) + bias[j + 3 * H];
-    gi = sigmoidf_(gi); gf = sigmoidf_(gf); gg = tanhf(gg); go = sigmoidf_(go);
-    const float c = gf * c_prev[(long)b * cp_rs + j] + gi * gg;
-    const float h = go * tanhf(c);
-    h_out[(long)b * ho_rs + j] = __float2bfloat16(h);
-    c_out[(long)b * co_rs + j] = c;
-    const long g0 = (long)b * go_rs + j;
-    gates_out[g0] = __float2bfloat16(gi);
-    gates_out[g0 + H] = __float2bfloat16(gf);
-    gates_out[g0 + 2 * H] = __float2bfloat16(gg);
-    gates_out[g0 + 3 * H] = __float2bfloat16(go);
+    const Cell cell = lstm_cell_at<CellFma::FC>(
+        qp[0], qp[1], qp[2], qp[3], xp + (long)b * xp_rs + j, bias + j, H,
+        c_prev[(long)b * cp_rs + j]);
+    store_cell(cell, h_out + (long)b * ho_rs + j, c_out + (long)b * co_rs + j,
+               gates_out + (long)b * go_rs + j, H);
   }
 }
 
@@ -277,8 +267,8 @@ template <int BM, int BN, int STAGES = 2>
 static void run_fused(at::Tensor& xp, at::Tensor& bias, at::Tensor& h0,
                       at::Tensor& c0, at::Tensor& w_hh, at::Tensor& hs,
                       at::Tensor& cs, at::Tensor& gates) {
-  const int T = xp.size(0), B = xp.size(1);   // TIME-MAJOR (T,B,·)
-  const int H = w_hh.size(1);
+  const SeqSteps<__hip_bfloat16> s(xp, bias, h0, c0, hs, cs, gates, w_hh.size(1));
+  const int B = s.B, H = s.H;
   const int MT = ceil_div(B, BM);
   const dim3 grid(MT * ceil_div(4 * H, BN));
   const size_t lds = std::max(
@@ -293,31 +283,19 @@ static void run_fused(at::Tensor& xp, at::Tensor& bias, at::Tensor& h0,
       attr_set = true;
     }
   }
-  auto* hsp = reinterpret_cast<__hip_bfloat16*>(hs.data_ptr());
-  auto* xpp = reinterpret_cast<const __hip_bfloat16*>(xp.data_ptr());
-  auto* gp = reinterpret_cast<__hip_bfloat16*>(gates.data_ptr());
   auto* wp = reinterpret_cast<const __hip_bfloat16*>(w_hh.data_ptr());
-  auto h0c = h0.contiguous();
-  auto* h0p = reinterpret_cast<const __hip_bfloat16*>(h0c.data_ptr());
-  for (int t = 0; t < T; ++t) {
-    const __hip_bfloat16* hp = (t == 0) ? h0p : hsp + (long)(t - 1) * B * H;
-    const float* cp = (t == 0) ? c0.data_ptr<float>()
-                               : cs.data_ptr<float>() + (long)(t - 1) * B * H;
+  for (int t = 0; t < s.T; ++t) {
     hipLaunchKernelGGL((lstm_cell_fused<BM, BN, STAGES>), grid, dim3(THREADS),
         lds, stream(),
-        hp, (long)H, wp, xpp + (long)t * B * 4 * H, (long)4 * H,
-        bias.data_ptr<float>(), cp, (long)H,
-        hsp + (long)t * B * H, (long)H,
-        cs.data_ptr<float>() + (long)t * B * H, (long)H,
-        gp + (long)t * B * 4 * H, (long)4 * H, B, H, MT);
+        s.h_prev(t), (long)H, wp, s.xp_at(t), (long)4 * H, s.bias(),
+        s.c_prev(t), (long)H, s.h_out(t), (long)H, s.c_out(t), (long)H,
+        s.gates_at(t), (long)4 * H, B, H, MT);
   }
 }
 
 void lstm_seq_forward_fused(at::Tensor xp, at::Tensor bias, at::Tensor h0,
                             at::Tensor c0, at::Tensor w_hh, at::Tensor hs,
                             at::Tensor cs, at::Tensor gates) {
-  CI_CHECK_CUDA(xp); CI_CHECK_CONTIG(xp); CI_CHECK_CONTIG(hs);
-  CI_CHECK_CONTIG(cs); CI_CHECK_CONTIG(gates); CI_CHECK_CONTIG(c0);
   TORCH_CHECK(xp.scalar_type() == at::ScalarType::BFloat16,
               "fused LSTM cell kernel is bf16; use CI_LSTM_MODE=lib for fp32");
   TORCH_CHECK(w_hh.is_contiguous(), "w_hh must be contiguous");

@@ -9,11 +9,115 @@
 // h/c/gates — a single launch per timestep replaces hipBLASLt GEMV +
 // pointwise kernel. Grid = H blocks (2400 at the deployed shape) fills
 // all 256 CUs; batch rows loop inside the block (B tiny).
-#include "common.h"
+#include "lstm_cell.h"
 
 namespace ci {
 
 typedef __bf16 bf16x8g __attribute__((ext_vector_type(8)));
+
+constexpr int BMAX = 8;  // dispatch guarantees B <= 8
+
+// ---- weight-row loaders: one row of W_hh as fp32, W elements per lane-step
+struct RowBf16 {
+  static constexpr int W = 8;
+  const __hip_bfloat16* row;
+  __device__ __forceinline__ void load(int k, float* w) const {
+    const bf16x8g v = *reinterpret_cast<const bf16x8g*>(row + k);
+    #pragma unroll
+    for (int e = 0; e < 8; ++e) w[e] = (float)v[e];
+  }
+  __device__ __forceinline__ float at(int k) const { return ld(row + k); }
+  __device__ __forceinline__ float scaled(float a) const { return a; }
+};
+
+struct RowFp8 {  // e4m3 row with its per-row scale
+  static constexpr int W = 16;
+  const unsigned char* row;
+  float scale;
+  __device__ __forceinline__ void load(int k, float* w) const {
+    const uint4 q = *reinterpret_cast<const uint4*>(row + k);  // 16 fp8
+    fp8x4_to_f32(q.x, w);
+    fp8x4_to_f32(q.y, w + 4);
+    fp8x4_to_f32(q.z, w + 8);
+    fp8x4_to_f32(q.w, w + 12);
+  }
+  __device__ __forceinline__ float at(int k) const {
+    float w1[4];
+    fp8x4_to_f32((unsigned int)row[k], w1);  // low byte -> w1[0]
+    return w1[0];
+  }
+  __device__ __forceinline__ float scaled(float a) const { return a * scale; }
+};
+
+// dots[b][wave] = <h_prev[b,:], wrow> for this wave's gate row, all b < B:
+// lane-split K, shfl reduction. Callers __syncthreads() before reading dots.
+template <typename WRow>
+static __device__ __forceinline__ void gemv_dots(
+    float (*dots)[4], const WRow& wrow,
+    const __hip_bfloat16* __restrict__ h_prev, long h_rs, int B, int H) {
+  constexpr int W = WRow::W;
+  const int wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  const int Hv = H / W * W;
+  // read each W element ONCE; accumulate all batch rows simultaneously
+  // (h rows are tiny and L2-resident; W is the 46 MB stream)
+  float acc[BMAX];
+  #pragma unroll
+  for (int b = 0; b < BMAX; ++b) acc[b] = 0.f;
+  // acc[] must be register-resident: unroll over BMAX with a guard so
+  // every index is compile-time (runtime-indexed arrays go to scratch —
+  // CDNA guide §5.4 rule 20)
+  for (int k = lane * W; k < Hv; k += 64 * W) {
+    float wf[W];
+    wrow.load(k, wf);
+    #pragma unroll
+    for (int b = 0; b < BMAX; ++b) {
+      if (b >= B) break;
+      #pragma unroll
+      for (int v = 0; v < W; v += 8) {
+        const bf16x8g hv = *reinterpret_cast<const bf16x8g*>(
+            h_prev + (long)b * h_rs + k + v);
+        #pragma unroll
+        for (int e = 0; e < 8; ++e) acc[b] += wf[v + e] * (float)hv[e];
+      }
+    }
+  }
+  for (int k = Hv + lane; k < H; k += 64) {
+    const float wv = wrow.at(k);
+    #pragma unroll
+    for (int b = 0; b < BMAX; ++b) {
+      if (b >= B) break;
+      acc[b] += wv * ld(h_prev + (long)b * h_rs + k);
+    }
+  }
+  #pragma unroll
+  for (int b = 0; b < BMAX; ++b) {
+    if (b >= B) break;
+    float a = wrow.scaled(acc[b]);
+    #pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+      a += __shfl_down(a, off);
+    if (lane == 0) dots[b][wave] = a;
+  }
+}
+
+// the block's first B threads finish hidden unit j from its four dots
+static __device__ __forceinline__ void gemv_finish(
+    const float (*dots)[4], int j,
+    const __hip_bfloat16* __restrict__ xp, long xp_rs,
+    const float* __restrict__ bias,
+    const float* __restrict__ c_prev, long cp_rs,
+    __hip_bfloat16* __restrict__ h_out, long ho_rs,
+    float* __restrict__ c_out, long co_rs,
+    __hip_bfloat16* __restrict__ gates_out, long go_rs, int B, int H) {
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    const Cell r = lstm_cell_at<CellFma::IG>(
+        dots[b][0], dots[b][1], dots[b][2], dots[b][3],
+        xp + (long)b * xp_rs + j, bias + j, H, c_prev[(long)b * cp_rs + j]);
+    store_cell(r, h_out + (long)b * ho_rs + j, c_out + (long)b * co_rs + j,
+               gates_out + (long)b * go_rs + j, H);
+  }
+}
 
 __global__ __launch_bounds__(256) void lstm_cell_gemv(
     const __hip_bfloat16* __restrict__ h_prev, long h_rs,
@@ -25,67 +129,13 @@ __global__ __launch_bounds__(256) void lstm_cell_gemv(
     float* __restrict__ c_out, long co_rs,
     __hip_bfloat16* __restrict__ gates_out, long go_rs,
     int B, int H) {
-  constexpr int BMAX = 8;            // dispatch guarantees B <= 8
   const int j = blockIdx.x;          // hidden unit
   const int wave = threadIdx.x >> 6; // gate g in {i,f,g,o}
-  const int lane = threadIdx.x & 63;
-  const __hip_bfloat16* wrow = w_hh + (long)(wave * H + j) * H;
   __shared__ float dots[BMAX][4];
-  const int Hv = H / 8 * 8;
-  // read each W element ONCE; accumulate all batch rows simultaneously
-  // (h rows are tiny and L2-resident; W is the 46 MB stream)
-  float acc[BMAX];
-  #pragma unroll
-  for (int b = 0; b < BMAX; ++b) acc[b] = 0.f;
-  // acc[] must be register-resident: unroll over BMAX with a guard so
-  // every index is compile-time (runtime-indexed arrays go to scratch —
-  // CDNA guide §5.4 rule 20)
-  for (int k = lane * 8; k < Hv; k += 64 * 8) {
-    bf16x8g wv = *reinterpret_cast<const bf16x8g*>(wrow + k);
-    #pragma unroll
-    for (int b = 0; b < BMAX; ++b) {
-      if (b >= B) break;
-      bf16x8g hv = *reinterpret_cast<const bf16x8g*>(
-          h_prev + (long)b * h_rs + k);
-      #pragma unroll
-      for (int e = 0; e < 8; ++e)
-        acc[b] += (float)wv[e] * (float)hv[e];
-    }
-  }
-  for (int k = Hv + lane; k < H; k += 64) {
-    const float wv = ld(wrow + k);
-    #pragma unroll
-    for (int b = 0; b < BMAX; ++b) {
-      if (b >= B) break;
-      acc[b] += wv * ld(h_prev + (long)b * h_rs + k);
-    }
-  }
-  #pragma unroll
-  for (int b = 0; b < BMAX; ++b) {
-    if (b >= B) break;
-    float a = acc[b];
-    #pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-      a += __shfl_down(a, off);
-    if (lane == 0) dots[b][wave] = a;
-  }
+  gemv_dots(dots, RowBf16{w_hh + (long)(wave * H + j) * H}, h_prev, h_rs, B, H);
   __syncthreads();
-  for (int b = threadIdx.x; b < B; b += blockDim.x) {
-    const long xo = (long)b * xp_rs + j;
-    const float gi = sigmoidf_(dots[b][0] + ld(xp + xo) + bias[j]);
-    const float gf = sigmoidf_(dots[b][1] + ld(xp + xo + H) + bias[j + H]);
-    const float gg = tanhf(dots[b][2] + ld(xp + xo + 2 * H) + bias[j + 2 * H]);
-    const float go = sigmoidf_(dots[b][3] + ld(xp + xo + 3 * H) + bias[j + 3 * H]);
-    const float c = gf * c_prev[(long)b * cp_rs + j] + gi * gg;
-    const float h = go * tanhf(c);
-    st(h_out + (long)b * ho_rs + j, h);
-    c_out[(long)b * co_rs + j] = c;
-    const long g0 = (long)b * go_rs + j;
-    st(gates_out + g0, gi);
-    st(gates_out + g0 + H, gf);
-    st(gates_out + g0 + 2 * H, gg);
-    st(gates_out + g0 + 3 * H, go);
-  }
+  gemv_finish(dots, j, xp, xp_rs, bias, c_prev, cp_rs, h_out, ho_rs,
+              c_out, co_rs, gates_out, go_rs, B, H);
 }
 
 // ---- persistent whole-sequence variant (CI_SERVE_PERSISTENT) ------------
@@ -145,72 +195,22 @@ __global__ __launch_bounds__(256) void lstm_seq_gemv_persistent(
     unsigned int* __restrict__ barrier_ws,   // [cnt, gen]
     int* __restrict__ fail_flag,
     int B, int H, int T) {
-  constexpr int BMAX = 8;
   const unsigned int NB = gridDim.x;
   const int wave = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const int Hv = H / 8 * 8;
   __shared__ float dots[BMAX][4];
   for (int t = 0; t < T; ++t) {
     const __hip_bfloat16* hp = (t == 0) ? h0 : hs + (long)(t - 1) * B * H;
     const float* cp = (t == 0) ? c0 : cs + (long)(t - 1) * B * H;
     const long h_prev_rs = (t == 0) ? h_rs : (long)H;
     const long c_prev_rs = (t == 0) ? cp_rs : (long)H;
-    const __hip_bfloat16* xpt = xp + (long)t * B * 4 * H;
-    __hip_bfloat16* h_out = hs + (long)t * B * H;
-    float* c_out = cs + (long)t * B * H;
-    __hip_bfloat16* g_out = gates_out + (long)t * B * 4 * H;
     for (int j = blockIdx.x; j < H; j += NB) {
-      const __hip_bfloat16* wrow = w_hh + (long)(wave * H + j) * H;
-      float acc[BMAX];
-      #pragma unroll
-      for (int b = 0; b < BMAX; ++b) acc[b] = 0.f;
-      for (int k = lane * 8; k < Hv; k += 64 * 8) {
-        bf16x8g wv = *reinterpret_cast<const bf16x8g*>(wrow + k);
-        #pragma unroll
-        for (int b = 0; b < BMAX; ++b) {
-          if (b >= B) break;
-          bf16x8g hv = *reinterpret_cast<const bf16x8g*>(
-              hp + (long)b * h_prev_rs + k);
-          #pragma unroll
-          for (int e = 0; e < 8; ++e)
-            acc[b] += (float)wv[e] * (float)hv[e];
-        }
-      }
-      for (int k = Hv + lane; k < H; k += 64) {
-        const float wv = ld(wrow + k);
-        #pragma unroll
-        for (int b = 0; b < BMAX; ++b) {
-          if (b >= B) break;
-          acc[b] += wv * ld(hp + (long)b * h_prev_rs + k);
-        }
-      }
-      #pragma unroll
-      for (int b = 0; b < BMAX; ++b) {
-        if (b >= B) break;
-        float a = acc[b];
-        #pragma unroll
-        for (int off = 32; off > 0; off >>= 1)
-          a += __shfl_down(a, off);
-        if (lane == 0) dots[b][wave] = a;
-      }
+      gemv_dots(dots, RowBf16{w_hh + (long)(wave * H + j) * H}, hp, h_prev_rs,
+                B, H);
       __syncthreads();
-      for (int b = threadIdx.x; b < B; b += blockDim.x) {
-        const long xo = (long)b * 4 * H + j;
-        const float gi = sigmoidf_(dots[b][0] + ld(xpt + xo) + bias[j]);
-        const float gf = sigmoidf_(dots[b][1] + ld(xpt + xo + H) + bias[j + H]);
-        const float gg = tanhf(dots[b][2] + ld(xpt + xo + 2 * H) + bias[j + 2 * H]);
-        const float go = sigmoidf_(dots[b][3] + ld(xpt + xo + 3 * H) + bias[j + 3 * H]);
-        const float c = gf * cp[(long)b * c_prev_rs + j] + gi * gg;
-        const float h = go * tanhf(c);
-        st(h_out + (long)b * H + j, h);
-        c_out[(long)b * H + j] = c;
-        const long g0 = (long)b * 4 * H + j;
-        st(g_out + g0, gi);
-        st(g_out + g0 + H, gf);
-        st(g_out + g0 + 2 * H, gg);
-        st(g_out + g0 + 3 * H, go);
-      }
+      gemv_finish(dots, j, xp + (long)t * B * 4 * H, (long)4 * H, bias,
+                  cp, c_prev_rs, hs + (long)t * B * H, (long)H,
+                  cs + (long)t * B * H, (long)H,
+                  gates_out + (long)t * B * 4 * H, (long)4 * H, B, H);
       __syncthreads();  // dots reused by the next j of this block
     }
     if (!grid_sync_capped(barrier_ws, barrier_ws + 1, NB)) {
@@ -224,33 +224,20 @@ __global__ __launch_bounds__(256) void lstm_seq_gemv_persistent(
 void lstm_seq_forward_gemv(at::Tensor xp, at::Tensor bias, at::Tensor h0,
                            at::Tensor c0, at::Tensor w_hh, at::Tensor hs,
                            at::Tensor cs, at::Tensor gates) {
-  CI_CHECK_CUDA(xp); CI_CHECK_CONTIG(xp); CI_CHECK_CONTIG(hs);
-  CI_CHECK_CONTIG(cs); CI_CHECK_CONTIG(gates); CI_CHECK_CONTIG(c0);
   TORCH_CHECK(xp.scalar_type() == at::ScalarType::BFloat16,
               "gemv cell kernel is bf16");
   TORCH_CHECK(w_hh.is_contiguous(), "w_hh must be contiguous");
-  const int T = xp.size(0), B = xp.size(1);
+  const SeqSteps<__hip_bfloat16> s(xp, bias, h0, c0, hs, cs, gates, w_hh.size(1));
+  const int B = s.B, H = s.H;
   TORCH_CHECK(B <= 8, "gemv cell kernel is for B <= 8 (got ", B, ")");
-  const int H = w_hh.size(1);
-  auto* hsp = reinterpret_cast<__hip_bfloat16*>(hs.data_ptr());
-  auto* xpp = reinterpret_cast<const __hip_bfloat16*>(xp.data_ptr());
-  auto* gp = reinterpret_cast<__hip_bfloat16*>(gates.data_ptr());
   auto* wp = reinterpret_cast<const __hip_bfloat16*>(w_hh.data_ptr());
-  auto h0c = h0.contiguous();
-  auto* h0p = reinterpret_cast<const __hip_bfloat16*>(h0c.data_ptr());
-  for (int t = 0; t < T; ++t) {
-    const __hip_bfloat16* hp = (t == 0) ? h0p : hsp + (long)(t - 1) * B * H;
-    const float* cp = (t == 0) ? c0.data_ptr<float>()
-                               : cs.data_ptr<float>() + (long)(t - 1) * B * H;
+  for (int t = 0; t < s.T; ++t) {
     hipLaunchKernelGGL(lstm_cell_gemv, dim3(H), dim3(256), 0, stream(),
-        hp, (long)H, wp, xpp + (long)t * B * 4 * H, (long)4 * H,
-        bias.data_ptr<float>(), cp, (long)H,
-        hsp + (long)t * B * H, (long)H,
-        cs.data_ptr<float>() + (long)t * B * H, (long)H,
-        gp + (long)t * B * 4 * H, (long)4 * H, B, H);
+        s.h_prev(t), (long)H, wp, s.xp_at(t), (long)4 * H, s.bias(),
+        s.c_prev(t), (long)H, s.h_out(t), (long)H, s.c_out(t), (long)H,
+        s.gates_at(t), (long)4 * H, B, H);
   }
 }
-
 
 // persistent driver: ONE launch for the whole sequence. Returns the grid
 // size used, or 0 when a co-resident grid is not available (caller falls
@@ -261,15 +248,13 @@ long lstm_seq_forward_gemv_persistent(at::Tensor xp, at::Tensor bias,
                                       at::Tensor w_hh, at::Tensor hs,
                                       at::Tensor cs, at::Tensor gates,
                                       at::Tensor ws) {
-  CI_CHECK_CUDA(xp); CI_CHECK_CONTIG(xp); CI_CHECK_CONTIG(hs);
-  CI_CHECK_CONTIG(cs); CI_CHECK_CONTIG(gates); CI_CHECK_CONTIG(ws);
-  CI_CHECK_CONTIG(c0);
+  CI_CHECK_CONTIG(ws);
   TORCH_CHECK(xp.scalar_type() == at::ScalarType::BFloat16);
   TORCH_CHECK(w_hh.is_contiguous(), "w_hh must be contiguous");
   TORCH_CHECK(ws.numel() >= 4 && ws.scalar_type() == at::ScalarType::Int);
-  const int T = xp.size(0), B = xp.size(1);
+  const SeqSteps<__hip_bfloat16> s(xp, bias, h0, c0, hs, cs, gates, w_hh.size(1));
+  const int B = s.B, H = s.H;
   TORCH_CHECK(B <= 8, "gemv persistent kernel is for B <= 8");
-  const int H = w_hh.size(1);
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
           &per_cu, reinterpret_cast<const void*>(&lstm_seq_gemv_persistent),
@@ -282,18 +267,14 @@ long lstm_seq_forward_gemv_persistent(at::Tensor xp, at::Tensor bias,
   if (const char* env = getenv("CI_PERS_NB")) {   // residency experiments
     nb = std::min<long>(std::max(1L, atol(env)), H);
   }
-  auto h0c = h0.contiguous();
   hipLaunchKernelGGL(lstm_seq_gemv_persistent, dim3(nb), dim3(256), 0,
       stream(),
-      reinterpret_cast<const __hip_bfloat16*>(h0c.data_ptr()), (long)H,
+      s.h_prev(0), (long)H,
       reinterpret_cast<const __hip_bfloat16*>(w_hh.data_ptr()),
-      reinterpret_cast<const __hip_bfloat16*>(xp.data_ptr()),
-      bias.data_ptr<float>(), c0.data_ptr<float>(), (long)H,
-      reinterpret_cast<__hip_bfloat16*>(hs.data_ptr()),
-      cs.data_ptr<float>(),
-      reinterpret_cast<__hip_bfloat16*>(gates.data_ptr()),
+      s.xp_at(0), s.bias(), s.c_prev(0), (long)H,
+      s.h_out(0), s.c_out(0), s.gates_at(0),
       reinterpret_cast<unsigned int*>(ws.data_ptr()),
-      reinterpret_cast<int*>(ws.data_ptr()) + 2, B, H, T);
+      reinterpret_cast<int*>(ws.data_ptr()) + 2, B, H, s.T);
   return nb;
 }
 
@@ -315,100 +296,32 @@ __global__ __launch_bounds__(256) void lstm_cell_gemv_fp8(
     float* __restrict__ c_out, long co_rs,
     __hip_bfloat16* __restrict__ gates_out, long go_rs,
     int B, int H) {
-  constexpr int BMAX = 8;
   const int j = blockIdx.x;
-  const int wave = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const int row = wave * H + j;
-  const unsigned char* wrow = w8 + (long)row * H;
+  const int row = (threadIdx.x >> 6) * H + j;
   __shared__ float dots[BMAX][4];
-  const int Hv = H / 16 * 16;
-  float acc[BMAX];
-  #pragma unroll
-  for (int b = 0; b < BMAX; ++b) acc[b] = 0.f;
-  float wf[16];
-  for (int k = lane * 16; k < Hv; k += 64 * 16) {
-    const uint4 wq = *reinterpret_cast<const uint4*>(wrow + k);  // 16 fp8
-    fp8x4_to_f32(wq.x, wf);
-    fp8x4_to_f32(wq.y, wf + 4);
-    fp8x4_to_f32(wq.z, wf + 8);
-    fp8x4_to_f32(wq.w, wf + 12);
-    #pragma unroll
-    for (int b = 0; b < BMAX; ++b) {
-      if (b >= B) break;
-      const bf16x8g h0v = *reinterpret_cast<const bf16x8g*>(
-          h_prev + (long)b * h_rs + k);
-      const bf16x8g h1v = *reinterpret_cast<const bf16x8g*>(
-          h_prev + (long)b * h_rs + k + 8);
-      #pragma unroll
-      for (int e = 0; e < 8; ++e) acc[b] += wf[e] * (float)h0v[e];
-      #pragma unroll
-      for (int e = 0; e < 8; ++e) acc[b] += wf[8 + e] * (float)h1v[e];
-    }
-  }
-  for (int k = Hv + lane; k < H; k += 64) {
-    float w1[4];
-    fp8x4_to_f32((unsigned int)wrow[k], w1);  // low byte -> w1[0]
-    #pragma unroll
-    for (int b = 0; b < BMAX; ++b) {
-      if (b >= B) break;
-      acc[b] += w1[0] * ld(h_prev + (long)b * h_rs + k);
-    }
-  }
-  const float sc = wscale[row];
-  #pragma unroll
-  for (int b = 0; b < BMAX; ++b) {
-    if (b >= B) break;
-    float a = acc[b] * sc;
-    #pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-      a += __shfl_down(a, off);
-    if (lane == 0) dots[b][wave] = a;
-  }
+  gemv_dots(dots, RowFp8{w8 + (long)row * H, wscale[row]}, h_prev, h_rs, B, H);
   __syncthreads();
-  for (int b = threadIdx.x; b < B; b += blockDim.x) {
-    const long xo = (long)b * xp_rs + j;
-    const float gi = sigmoidf_(dots[b][0] + ld(xp + xo) + bias[j]);
-    const float gf = sigmoidf_(dots[b][1] + ld(xp + xo + H) + bias[j + H]);
-    const float gg = tanhf(dots[b][2] + ld(xp + xo + 2 * H) + bias[j + 2 * H]);
-    const float go = sigmoidf_(dots[b][3] + ld(xp + xo + 3 * H) + bias[j + 3 * H]);
-    const float c = gf * c_prev[(long)b * cp_rs + j] + gi * gg;
-    const float h = go * tanhf(c);
-    st(h_out + (long)b * ho_rs + j, h);
-    c_out[(long)b * co_rs + j] = c;
-    const long g0 = (long)b * go_rs + j;
-    st(gates_out + g0, gi);
-    st(gates_out + g0 + H, gf);
-    st(gates_out + g0 + 2 * H, gg);
-    st(gates_out + g0 + 3 * H, go);
-  }
+  gemv_finish(dots, j, xp, xp_rs, bias, c_prev, cp_rs, h_out, ho_rs,
+              c_out, co_rs, gates_out, go_rs, B, H);
 }
 
 void lstm_seq_forward_gemv_fp8(at::Tensor xp, at::Tensor bias, at::Tensor h0,
                                at::Tensor c0, at::Tensor w8, at::Tensor wscale,
                                at::Tensor hs, at::Tensor cs, at::Tensor gates) {
-  CI_CHECK_CUDA(xp); CI_CHECK_CONTIG(xp); CI_CHECK_CONTIG(hs);
-  CI_CHECK_CONTIG(cs); CI_CHECK_CONTIG(gates); CI_CHECK_CONTIG(w8);
-  CI_CHECK_CONTIG(c0);
-  const int T = xp.size(0), B = xp.size(1);
+  CI_CHECK_CONTIG(w8);
+  TORCH_CHECK(xp.scalar_type() == at::ScalarType::BFloat16,
+              "fp8 gemv kernel is bf16-activation only");
+  TORCH_CHECK(w8.scalar_type() == at::ScalarType::Byte,
+              "w8 must hold e4m3 bytes (uint8)");
+  const SeqSteps<__hip_bfloat16> s(xp, bias, h0, c0, hs, cs, gates, w8.size(1));
+  const int B = s.B, H = s.H;
   TORCH_CHECK(B <= 8, "fp8 gemv kernel is for B <= 8");
-  const int H = w8.size(1);
-  auto* hsp = reinterpret_cast<__hip_bfloat16*>(hs.data_ptr());
-  auto* xpp = reinterpret_cast<const __hip_bfloat16*>(xp.data_ptr());
-  auto* gp = reinterpret_cast<__hip_bfloat16*>(gates.data_ptr());
-  auto h0c = h0.contiguous();
-  auto* h0p = reinterpret_cast<const __hip_bfloat16*>(h0c.data_ptr());
-  for (int t = 0; t < T; ++t) {
-    const __hip_bfloat16* hp = (t == 0) ? h0p : hsp + (long)(t - 1) * B * H;
-    const float* cp = (t == 0) ? c0.data_ptr<float>()
-                               : cs.data_ptr<float>() + (long)(t - 1) * B * H;
+  for (int t = 0; t < s.T; ++t) {
     hipLaunchKernelGGL(lstm_cell_gemv_fp8, dim3(H), dim3(256), 0, stream(),
-        hp, (long)H, w8.data_ptr<unsigned char>(), wscale.data_ptr<float>(),
-        xpp + (long)t * B * 4 * H, (long)4 * H,
-        bias.data_ptr<float>(), cp, (long)H,
-        hsp + (long)t * B * H, (long)H,
-        cs.data_ptr<float>() + (long)t * B * H, (long)H,
-        gp + (long)t * B * 4 * H, (long)4 * H, B, H);
+        s.h_prev(t), (long)H, w8.data_ptr<unsigned char>(),
+        wscale.data_ptr<float>(), s.xp_at(t), (long)4 * H, s.bias(),
+        s.c_prev(t), (long)H, s.h_out(t), (long)H, s.c_out(t), (long)H,
+        s.gates_at(t), (long)4 * H, B, H);
   }
 }
 

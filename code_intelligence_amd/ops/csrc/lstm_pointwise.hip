@@ -3,7 +3,7 @@
 // activation + c/h update (and their backward) are fused HIP kernels.
 // Reference semantics: fastai AWD_LSTM nn.LSTM cell, gate order i,f,g,o
 // (/root/reference/Issue_Embeddings/train.py:88-92).
-#include "common.h"
+#include "lstm_cell.h"
 
 #include <hip/hip_fp8.h>
 
@@ -16,12 +16,13 @@ constexpr float kH8Scale = 448.0f;
 
 void quantize_e4m3(at::Tensor src, at::Tensor dst, at::Tensor scale);  // fp8util.hip
 
-// VEC consecutive j per thread with 16-B vector loads/stores: ldv/stv
-// helpers live in common.h. Scalar tail path covers H % VEC != 0.
+// VEC consecutive j per thread with 16-B vector loads/stores (ldv/stv in
+// common.h) over columns [j0, j0 + ncol); the H % VEC columns left over run
+// the same body with VECTOR = false (VEC = 1).
 
 // one thread per (b, j-block): gates = xp + rec (+bias); c' = f*c + i*g;
 // h' = o*tanh(c')
-template <typename T>
+template <typename T, bool VECTOR>
 __global__ void lstm_cell_fwd(
     const T* __restrict__ xp, long xp_rs,      // (B,4H) view, row stride xp_rs
     const T* __restrict__ rec, long rec_rs,    // (B,4H) recurrent GEMM out
@@ -31,86 +32,53 @@ __global__ void lstm_cell_fwd(
     float* __restrict__ c_out, long c_rs,
     T* __restrict__ gates_out, long g_rs,      // post-activation i,f,g,o
     unsigned char* __restrict__ h8_out,        // optional e4m3(h*448)
-    int B, int H) {
-  constexpr int VEC = 16 / sizeof(T);
-  const int Hv = H / VEC;  // vector blocks per row (tail handled scalar)
+    int B, int H, int j0, int ncol) {
+  constexpr int VEC = VECTOR ? 16 / (int)sizeof(T) : 1;
+  constexpr CellFma FMA = VECTOR ? CellFma::IG : CellFma::FC;
+  const int nv = ncol / VEC;  // column blocks per row
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (long)B * Hv) return;
-  const int b = idx / Hv, j = (idx % Hv) * VEC;
+  if (idx >= (long)B * nv) return;
+  const int b = idx / nv, j = j0 + (idx % nv) * VEC;
   const long xo = (long)b * xp_rs + j;
   const long ro = (long)b * rec_rs + j;
   float gi[VEC], gf[VEC], gg[VEC], go[VEC], tmp[VEC], cprev[VEC];
   ldv<T, VEC>(xp + xo, gi); ldv<T, VEC>(rec + ro, tmp);
   #pragma unroll
-  for (int e = 0; e < VEC; ++e) gi[e] = sigmoidf_(gi[e] + tmp[e] + bias[j + e]);
+  for (int e = 0; e < VEC; ++e) gi[e] = (tmp[e] + gi[e]) + bias[j + e];
   ldv<T, VEC>(xp + xo + H, gf); ldv<T, VEC>(rec + ro + H, tmp);
   #pragma unroll
-  for (int e = 0; e < VEC; ++e) gf[e] = sigmoidf_(gf[e] + tmp[e] + bias[j + H + e]);
+  for (int e = 0; e < VEC; ++e) gf[e] = (tmp[e] + gf[e]) + bias[j + H + e];
   ldv<T, VEC>(xp + xo + 2 * H, gg); ldv<T, VEC>(rec + ro + 2 * H, tmp);
   #pragma unroll
-  for (int e = 0; e < VEC; ++e) gg[e] = tanhf(gg[e] + tmp[e] + bias[j + 2 * H + e]);
+  for (int e = 0; e < VEC; ++e) gg[e] = (tmp[e] + gg[e]) + bias[j + 2 * H + e];
   ldv<T, VEC>(xp + xo + 3 * H, go); ldv<T, VEC>(rec + ro + 3 * H, tmp);
   #pragma unroll
-  for (int e = 0; e < VEC; ++e) go[e] = sigmoidf_(go[e] + tmp[e] + bias[j + 3 * H + e]);
+  for (int e = 0; e < VEC; ++e) go[e] = (tmp[e] + go[e]) + bias[j + 3 * H + e];
   ldv_f32<VEC>(c_prev + (long)b * cp_rs + j, cprev);
   float c[VEC], h[VEC];
   #pragma unroll
   for (int e = 0; e < VEC; ++e) {
-    c[e] = gf[e] * cprev[e] + gi[e] * gg[e];
-    h[e] = go[e] * tanhf(c[e]);
+    const Cell r = lstm_cell<FMA>(gi[e], gf[e], gg[e], go[e], cprev[e]);
+    gi[e] = r.i; gf[e] = r.f; gg[e] = r.g; go[e] = r.o; c[e] = r.c; h[e] = r.h;
   }
-  stv<T, VEC>(h_out + (long)b * h_rs + j, h);
   if (h8_out != nullptr) {
     unsigned char q[VEC];
     #pragma unroll
     for (int e = 0; e < VEC; ++e)
       q[e] = __hip_fp8_e4m3(h[e] * kH8Scale).__x;
+    unsigned char* h8 = h8_out + (long)b * h_rs + j;
     if constexpr (VEC == 8) {
-      *reinterpret_cast<uint2*>(h8_out + (long)b * h_rs + j) =
-          *reinterpret_cast<const uint2*>(q);
-    } else {
-      *reinterpret_cast<unsigned int*>(h8_out + (long)b * h_rs + j) =
+      *reinterpret_cast<uint2*>(h8) = *reinterpret_cast<const uint2*>(q);
+    } else if constexpr (VEC == 4) {
+      *reinterpret_cast<unsigned int*>(h8) =
           *reinterpret_cast<const unsigned int*>(q);
+    } else {
+      *h8 = q[0];
     }
   }
-  stv_f32<VEC>(c_out + (long)b * c_rs + j, c);
-  const long gout = (long)b * g_rs + j;
-  stv<T, VEC>(gates_out + gout, gi);
-  stv<T, VEC>(gates_out + gout + H, gf);
-  stv<T, VEC>(gates_out + gout + 2 * H, gg);
-  stv<T, VEC>(gates_out + gout + 3 * H, go);
-}
-
-// scalar tail kernel for H % VEC != 0 columns
-template <typename T>
-__global__ void lstm_cell_fwd_tail(
-    const T* __restrict__ xp, long xp_rs, const T* __restrict__ rec, long rec_rs,
-    const float* __restrict__ bias, const float* __restrict__ c_prev, long cp_rs,
-    T* __restrict__ h_out, long h_rs, float* __restrict__ c_out, long c_rs,
-    T* __restrict__ gates_out, long g_rs, unsigned char* __restrict__ h8_out,
-    int B, int H, int j0) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int ncol = H - j0;
-  if (idx >= (long)B * ncol) return;
-  const int b = idx / ncol, j = j0 + idx % ncol;
-  const long xo = (long)b * xp_rs + j;
-  const long ro = (long)b * rec_rs + j;
-  float gi = ld(xp + xo) + ld(rec + ro) + bias[j];
-  float gf = ld(xp + xo + H) + ld(rec + ro + H) + bias[j + H];
-  float gg = ld(xp + xo + 2 * H) + ld(rec + ro + 2 * H) + bias[j + 2 * H];
-  float go = ld(xp + xo + 3 * H) + ld(rec + ro + 3 * H) + bias[j + 3 * H];
-  gi = sigmoidf_(gi); gf = sigmoidf_(gf); gg = tanhf(gg); go = sigmoidf_(go);
-  const float c = gf * c_prev[(long)b * cp_rs + j] + gi * gg;
-  const float h = go * tanhf(c);
-  st(h_out + (long)b * h_rs + j, h);
-  if (h8_out != nullptr)
-    h8_out[(long)b * h_rs + j] = __hip_fp8_e4m3(h * kH8Scale).__x;
-  c_out[(long)b * c_rs + j] = c;
-  const long gout = (long)b * g_rs + j;
-  st(gates_out + gout, gi);
-  st(gates_out + gout + H, gf);
-  st(gates_out + gout + 2 * H, gg);
-  st(gates_out + gout + 3 * H, go);
+  store_cells<T, VEC>(h, c, gi, gf, gg, go, h_out + (long)b * h_rs + j,
+                      c_out + (long)b * c_rs + j,
+                      gates_out + (long)b * g_rs + j, H);
 }
 
 // backward pointwise: consumes dh_ext (upstream) + dh_rec (t+1 GEMM),
@@ -190,68 +158,50 @@ __global__ void lstm_cell_bwd(
   }
 }
 
-template <typename ST>
-static void launch_fwd_step(const at::Tensor& xp, const at::Tensor& bias,
-                            const at::Tensor& rec, const at::Tensor& c_prev,
-                            long cp_off, long cp_rs, at::Tensor& hs,
-                            at::Tensor& cs, at::Tensor& gates, int t, int B,
-                            int T, int H, unsigned char* h8_base = nullptr) {
-  // TIME-MAJOR layout: xp/hs/cs/gates are (T, B, ·) contiguous, so slice t
-  // is a contiguous (B, ·) block — hipBLASLt sees contiguous operands and
-  // the cell kernel gets unit row strides.
-  // 64-thread blocks quadruple the workgroup count (the deployed shape
-  // yields only 600 WGs at 256 threads = 2.3/CU and the kernel is
-  // latency-bound; measured 432.3 vs 435.2 ms/step e2e at 64 vs 256) —
-  // CI_CELL_THREADS overrides.
+// 64-thread blocks quadruple the workgroup count (the deployed shape
+// yields only 600 WGs at 256 threads = 2.3/CU and the kernel is
+// latency-bound; measured 432.3 vs 435.2 ms/step e2e at 64 vs 256) —
+// CI_CELL_THREADS overrides. Forward and backward cell kernels share it.
+static int cell_threads() {
   static const int threads = [] {
     const char* e = getenv("CI_CELL_THREADS");
     return e ? atoi(e) : 64;
   }();
+  return threads;
+}
+
+// step t of s from rec = h_prev @ w_hh^T: a vector launch over the H / VEC
+// column blocks, a scalar launch over the H % VEC columns that remain
+template <typename ST>
+static void launch_fwd_step(const SeqSteps<ST>& s, int t, const at::Tensor& rec,
+                            unsigned char* h8_base = nullptr) {
+  const int threads = cell_threads();
   constexpr int VEC = 16 / sizeof(ST);
-  const int Hv = H / VEC;
-  const ST* xpp = reinterpret_cast<const ST*>(xp.data_ptr()) + (long)t * B * 4 * H;
-  const ST* recp = reinterpret_cast<const ST*>(rec.data_ptr());
-  ST* hp = reinterpret_cast<ST*>(hs.data_ptr()) + (long)t * B * H;
-  float* cp = cs.data_ptr<float>() + (long)t * B * H;
-  ST* gp = reinterpret_cast<ST*>(gates.data_ptr()) + (long)t * B * 4 * H;
+  const int B = s.B, H = s.H, nvec = H / VEC * VEC;
   unsigned char* h8p = h8_base ? h8_base + (long)t * B * H : nullptr;
-  if (Hv > 0) {
-    hipLaunchKernelGGL((lstm_cell_fwd<ST>),
-        dim3(ceil_div((long)B * Hv, threads)), dim3(threads), 0, stream(),
-        xpp, (long)4 * H, recp, (long)4 * H, bias.data_ptr<float>(),
-        c_prev.data_ptr<float>() + cp_off, cp_rs,
-        hp, (long)H, cp, (long)H, gp, (long)4 * H, h8p, B, H);
-  }
-  if (H % VEC) {
-    const int j0 = Hv * VEC;
-    hipLaunchKernelGGL((lstm_cell_fwd_tail<ST>),
-        dim3(ceil_div((long)B * (H - j0), threads)), dim3(threads), 0, stream(),
-        xpp, (long)4 * H, recp, (long)4 * H, bias.data_ptr<float>(),
-        c_prev.data_ptr<float>() + cp_off, cp_rs,
-        hp, (long)H, cp, (long)H, gp, (long)4 * H, h8p, B, H, j0);
-  }
+  auto launch = [&](auto kern, int j0, int ncol, int per_thread) {
+    hipLaunchKernelGGL(kern,
+        dim3(ceil_div((long)B * (ncol / per_thread), threads)), dim3(threads),
+        0, stream(),
+        s.xp_at(t), (long)4 * H, reinterpret_cast<const ST*>(rec.data_ptr()),
+        (long)4 * H, s.bias(), s.c_prev(t), (long)H, s.h_out(t), (long)H,
+        s.c_out(t), (long)H, s.gates_at(t), (long)4 * H, h8p, B, H, j0, ncol);
+  };
+  if (nvec > 0) launch(lstm_cell_fwd<ST, true>, 0, nvec, VEC);
+  if (H > nvec) launch(lstm_cell_fwd<ST, false>, nvec, H - nvec, 1);
 }
 
 // hs,cs,gates are (T,B,·) preallocated; xp (T,B,4H); h0 (B,H); c0 fp32 (B,H).
 void lstm_seq_forward_lib(at::Tensor xp, at::Tensor bias, at::Tensor h0,
                           at::Tensor c0, at::Tensor w_hh, at::Tensor hs,
                           at::Tensor cs, at::Tensor gates) {
-  CI_CHECK_CUDA(xp); CI_CHECK_CONTIG(xp); CI_CHECK_CONTIG(hs);
-  CI_CHECK_CONTIG(cs); CI_CHECK_CONTIG(gates); CI_CHECK_CONTIG(c0);
-  const int T = xp.size(0), B = xp.size(1);
-  const int H = w_hh.size(1);
   auto w_hh_t = w_hh.t();
-  auto rec = at::empty({B, 4 * H}, xp.options());
   CI_DISPATCH_FB(xp.scalar_type(), "lstm_seq_forward_lib", [&] {
-    for (int t = 0; t < T; ++t) {
-      auto h_prev = (t == 0) ? h0 : hs.select(0, t - 1);
-      at::mm_out(rec, h_prev, w_hh_t);
-      if (t == 0) {
-        launch_fwd_step<scalar_t>(xp, bias, rec, c0, 0, H, hs, cs, gates, t, B, T, H);
-      } else {
-        launch_fwd_step<scalar_t>(xp, bias, rec, cs, (long)(t - 1) * B * H,
-                                  (long)H, hs, cs, gates, t, B, T, H);
-      }
+    const SeqSteps<scalar_t> s(xp, bias, h0, c0, hs, cs, gates, w_hh.size(1));
+    auto rec = at::empty({s.B, 4 * s.H}, xp.options());
+    for (int t = 0; t < s.T; ++t) {
+      at::mm_out(rec, t == 0 ? h0 : hs.select(0, t - 1), w_hh_t);
+      launch_fwd_step(s, t, rec);
     }
   });
 }
@@ -265,14 +215,12 @@ void lstm_seq_forward_lib(at::Tensor xp, at::Tensor bias, at::Tensor h0,
 void lstm_seq_forward_lib_fp8(at::Tensor xp, at::Tensor bias, at::Tensor h0,
                               at::Tensor c0, at::Tensor w8, at::Tensor wscale,
                               at::Tensor hs, at::Tensor cs, at::Tensor gates) {
-  CI_CHECK_CUDA(xp); CI_CHECK_CONTIG(xp); CI_CHECK_CONTIG(hs);
-  CI_CHECK_CONTIG(cs); CI_CHECK_CONTIG(gates); CI_CHECK_CONTIG(w8);
-  CI_CHECK_CONTIG(c0);
+  CI_CHECK_CONTIG(w8);
   TORCH_CHECK(xp.scalar_type() == at::ScalarType::BFloat16,
               "fp8 recurrent path is bf16-activation only");
   TORCH_CHECK(w8.scalar_type() == at::ScalarType::Float8_e4m3fn);
-  const int T = xp.size(0), B = xp.size(1);
-  const int H = w8.size(1);
+  const SeqSteps<__hip_bfloat16> s(xp, bias, h0, c0, hs, cs, gates, w8.size(1));
+  const int T = s.T, B = s.B, H = s.H;
   auto w8_t = w8.t();  // (H, 4H) column-major for _scaled_mm mat2
   auto rec = at::empty({B, 4 * H}, xp.options());
   auto hs8 = at::empty({T, B, H},
@@ -284,19 +232,12 @@ void lstm_seq_forward_lib_fp8(at::Tensor xp, at::Tensor bias, at::Tensor h0,
                         xp.options().dtype(at::ScalarType::Float8_e4m3fn));
   quantize_e4m3(h0.contiguous(), h0_8, h8_scale);
   auto* h8_base = reinterpret_cast<unsigned char*>(hs8.data_ptr());
-  using ST = __hip_bfloat16;
   for (int t = 0; t < T; ++t) {
     auto h8_prev = (t == 0) ? h0_8 : hs8.select(0, t - 1);
     at::_scaled_mm_out(rec, h8_prev, w8_t, h8_scale, wscale,
                        c10::nullopt, c10::nullopt,
                        at::ScalarType::BFloat16, false);
-    if (t == 0) {
-      launch_fwd_step<ST>(xp, bias, rec, c0, 0, H, hs, cs, gates, t, B, T, H,
-                          h8_base);
-    } else {
-      launch_fwd_step<ST>(xp, bias, rec, cs, (long)(t - 1) * B * H, (long)H,
-                          hs, cs, gates, t, B, T, H, h8_base);
-    }
+    launch_fwd_step(s, t, rec, h8_base);
   }
 }
 
@@ -318,10 +259,7 @@ void lstm_seq_backward(at::Tensor dhs, at::Tensor dhT, at::Tensor dcT,
   // (scripts/gemm_probe.py on MI355X)
   auto w_hh_tc = w_hh.t().contiguous();
   auto w_hh_nt = w_hh_tc.t();
-  static const int threads = [] {
-    const char* e = getenv("CI_CELL_THREADS");
-    return e ? atoi(e) : 64;
-  }();
+  const int threads = cell_threads();
   CI_DISPATCH_FB(dhs.scalar_type(), "lstm_seq_backward", [&] {
     constexpr int VEC = 16 / sizeof(scalar_t);
     const bool vec_ok = (H % VEC) == 0;

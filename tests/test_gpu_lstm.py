@@ -12,7 +12,7 @@ would cause.
 
 Measured on MI355X, worst err/allowed over each driver's cases (K = 2):
   driver (cases)                          hs     cs     gates
-  lstm_seq_forward_lib fp32 (2e-4 flat)   3e-4   4e-4   4e-4
+  lstm_seq_forward_lib fp32 (2e-4 flat)   5e-4   4e-4   4e-4
   lstm_seq_forward_lib bf16               0.34   0.50   0.39
   lstm_seq_forward_fused, all 4 variants  0.35   0.50   0.41
   lstm_seq_forward_gemv                   0.33   0.50   0.39
@@ -129,7 +129,7 @@ def test_forward_lib_fp32(B, H, T):
 @pytest.mark.parametrize("B,H,T", _cases("lib_bf16"))
 def test_forward_lib_bf16(B, H, T):
     """The default training path. (5,20) and (2,5) run
-    lstm_cell_fwd_tail<bf16>; (67,8) leaves the last 64-thread block
+    lstm_cell_fwd<bf16, false>; (67,8) leaves the last 64-thread block
     partly idle."""
     _check_forward("lib_bf16", B, H, T)
 
