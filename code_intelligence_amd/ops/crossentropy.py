@@ -93,8 +93,9 @@ def _ce_overlap_enabled() -> bool:
 class _FusedCEFp8Function(torch.autograd.Function):
     """fp8-GEMM variant of the fused tied-decoder CE (see _fp8r_enabled).
     Loss/grad parity vs the bf16 path is locked by
-    tests/test_gpu_kernels.py (loss <2%, grad cosine >0.98) and the
-    markov convergence check in profiles/BENCH_HISTORY.md."""
+    tests/test_gpu_kernels.py (loss <2%, grad cosine >0.98), every
+    sub-path vs fp64 by tests/test_gpu_ce.py, and convergence by the
+    markov check in profiles/BENCH_HISTORY.md."""
 
     @staticmethod
     def forward(ctx, h: Tensor, weight: Tensor, bias: Tensor, targets: Tensor):
@@ -169,6 +170,11 @@ class _FusedCEFp8Function(torch.autograd.Function):
         ctx.save_for_backward(h, weight, b32, tgt64, lse, w8, sw)
         ctx.logits_full = logits_full
         ctx.dlog8_full = dlog8_full
+        # the recompute fallback must rebuild each chunk's logits with the
+        # GEMM that produced them here (lse belongs to THOSE logits), so it
+        # needs the e4m3 activations and their scale: O(N*H) bytes
+        ctx.h8 = h8 if logits_full is None else None
+        ctx.sa = sa
         ctx.chunk = C
         ctx.has_bias = bias is not None
         ctx.bias_dtype = bias.dtype if bias is not None else None
@@ -181,6 +187,8 @@ class _FusedCEFp8Function(torch.autograd.Function):
         h, weight, b32, targets, lse, w8, sw = ctx.saved_tensors
         logits_full = ctx.logits_full
         ctx.logits_full = None
+        h8, sa = ctx.h8, ctx.sa
+        ctx.h8 = None
         # set by forward's one-pass epilogue: logits_full already holds
         # bf16 (softmax-onehot)/N and dlog8_full its e4m3*448 copy
         dlog8_full = ctx.dlog8_full
@@ -189,7 +197,8 @@ class _FusedCEFp8Function(torch.autograd.Function):
         has_bias = ctx.has_bias
         N, H = h.shape
         V = weight.shape[0]
-        C = ctx.chunk if onepass else _FusedCEFunction.CHUNK
+        # forward's chunking: which GEMM a chunk takes depends on its size
+        C = ctx.chunk
         dev = h.device
         dh = torch.empty_like(h)
         scale = (dloss / N).to(torch.float32).reshape(1)
@@ -211,6 +220,7 @@ class _FusedCEFp8Function(torch.autograd.Function):
             torch.empty(min(C, N), V, dtype=h.dtype, device=dev)
         # (V, H) column-major e4m3 weight for the fp8 dh GEMM
         w8_cm = w8.t().contiguous().t()
+        w8_t = w8.t()
         w_t = weight.t()
         bias_arg = b32 if has_bias else _empty_f32(dev)
         overlap = _ce_overlap_enabled() and logits_full is not None
@@ -219,11 +229,18 @@ class _FusedCEFp8Function(torch.autograd.Function):
         for s in range(0, N, C):
             e = min(N, s + C)
             c = e - s
+            fp8_chunk = c % 16 == 0 and H % 16 == 0 and V % 16 == 0
             if logits_full is not None:
                 dlog = logits_full[s:e]
             else:
+                # same GEMM as forward's for this chunk: a bf16 recompute
+                # of fp8-GEMM logits would not match the saved lse
                 dlog = recompute[:c]
-                torch.mm(h[s:e], w_t, out=dlog)
+                if fp8_chunk:
+                    torch._scaled_mm(h8[s:e], w8_t, scale_a=sa, scale_b=sw,
+                                     out_dtype=h.dtype, out=dlog)
+                else:
+                    torch.mm(h[s:e], w_t, out=dlog)
             if onepass:
                 dlog8 = dlog8_full[s:e]
             else:
@@ -232,7 +249,7 @@ class _FusedCEFp8Function(torch.autograd.Function):
                 lib.ce_dlogits_dual(dlog, targets[s:e], bias_arg, lse[s:e],
                                     scale, scratch8, _STORE)
                 dlog8 = scratch8[:c]
-            if c % 16 == 0 and H % 16 == 0 and V % 16 == 0:
+            if fp8_chunk:
                 torch._scaled_mm(dlog8, w8_cm, scale_a=sc_over_store,
                                  scale_b=sw, out_dtype=h.dtype, out=dh[s:e])
             else:
@@ -294,6 +311,7 @@ class _FusedCEFunction(torch.autograd.Function):
         loss = (lse - tgt_logit).mean()
         ctx.save_for_backward(h, weight, b32, tgt64, lse)
         ctx.logits_full = logits_full
+        ctx.chunk = C
         ctx.has_bias = bias is not None
         ctx.bias_dtype = bias.dtype if bias is not None else None
         return loss
@@ -307,7 +325,7 @@ class _FusedCEFunction(torch.autograd.Function):
         has_bias = ctx.has_bias
         N, H = h.shape
         V = weight.shape[0]
-        C = _FusedCEFunction.CHUNK
+        C = ctx.chunk
         dh = torch.empty_like(h)
         scale = (dloss / N).to(torch.float32).reshape(1)
         scratch = None if logits_full is not None else \

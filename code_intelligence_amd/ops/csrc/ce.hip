@@ -120,6 +120,20 @@ void ce_rowstats(at::Tensor logits, at::Tensor targets, at::Tensor bias,
   });
 }
 
+// (p - onehot) * sc for the in-place store. At the target column p - 1
+// rounds at 2^-25, as much as the fp32 result's own half-ulp, so the plain
+// form rounds twice; an fp32 store gets the single-rounding fma instead. A
+// bf16 store's half-ulp (2^-9) hides the difference, and the bf16 instances
+// keep the plain form and their bits.
+template <typename T>
+static __device__ __forceinline__ float dlogit(float p, bool hot, float sc) {
+  if constexpr (sizeof(T) == 4) {
+    return hot ? __builtin_fmaf(p, sc, -sc) : p * sc;
+  } else {
+    return (hot ? p - 1.f : p) * sc;
+  }
+}
+
 // in-place: logits <- (exp(logits + bias - lse) - onehot) * scale
 template <typename T, int THREADS, bool HAS_BIAS>
 __global__ void ce_dlogits_kernel(T* __restrict__ logits, long row_stride,
@@ -145,16 +159,14 @@ __global__ void ce_dlogits_kernel(T* __restrict__ logits, long row_stride,
     T buf[VEC];
     #pragma unroll
     for (int e = 0; e < VEC; ++e) {
-      float p = __expf(v8[e] - l);
-      if (v + e == tgt) p -= 1.f;
-      st(buf + e, p * sc);
+      const float p = __expf(v8[e] - l);
+      st(buf + e, dlogit<T>(p, v + e == tgt, sc));
     }
     *reinterpret_cast<int4*>(x + v) = *reinterpret_cast<const int4*>(buf);
   }
   for (int v = Vv + threadIdx.x; v < V; v += THREADS) {
-    float p = __expf(ld(x + v) + (HAS_BIAS ? bias[v] : 0.f) - l);
-    if (v == tgt) p -= 1.f;
-    st(x + v, p * sc);
+    const float p = __expf(ld(x + v) + (HAS_BIAS ? bias[v] : 0.f) - l);
+    st(x + v, dlogit<T>(p, v == tgt, sc));
   }
 }
 
@@ -219,8 +231,8 @@ __global__ void ce_dlogits_dual_kernel(T* __restrict__ logits, long row_stride,
     #pragma unroll
     for (int e = 0; e < VEC; ++e) {
       float p = __expf(v8[e] - l);
+      st(buf + e, dlogit<T>(p, v + e == tgt, sc));
       if (v + e == tgt) p -= 1.f;
-      st(buf + e, p * sc);
       q8[e] = __hip_fp8_e4m3(p * store_scale).__x;
     }
     *reinterpret_cast<int4*>(x + v) = *reinterpret_cast<const int4*>(buf);
@@ -233,8 +245,8 @@ __global__ void ce_dlogits_dual_kernel(T* __restrict__ logits, long row_stride,
   }
   for (int v = Vv + threadIdx.x; v < V; v += THREADS) {
     float p = __expf(ld(x + v) + (HAS_BIAS ? bias[v] : 0.f) - l);
+    st(x + v, dlogit<T>(p, v == tgt, sc));
     if (v == tgt) p -= 1.f;
-    st(x + v, p * sc);
     s8[v] = __hip_fp8_e4m3(p * store_scale).__x;
   }
 }

@@ -8,12 +8,22 @@
 
 namespace ci {
 
+// One rounding rule for every element: the correctly rounded fp32 division
+// (v * (1/scale) double-rounds and can land on the other side of an e4m3
+// tie), saturation to +-448, and NaN kept as the e4m3 NaN code (fminf/fmaxf
+// would turn it into -448).
+static __device__ __forceinline__ unsigned char quant_e4m3(float v, float s) {
+  const float r = v / s;
+  if (r != r) return 0x7f;
+  return __hip_fp8_e4m3(fminf(fmaxf(r, -448.f), 448.f)).__x;
+}
+
 template <typename T>
 __global__ void quantize_e4m3_kernel(const T* __restrict__ src,
                                      unsigned char* __restrict__ dst, long n,
                                      const float* __restrict__ scale) {
   constexpr int VEC = 16 / sizeof(T);
-  const float inv = 1.0f / scale[0];
+  const float s = scale[0];
   const long base = ((long)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
   if (base >= n) return;
   if (base + VEC <= n) {
@@ -22,7 +32,7 @@ __global__ void quantize_e4m3_kernel(const T* __restrict__ src,
     unsigned char q[VEC];
     #pragma unroll
     for (int e = 0; e < VEC; ++e)
-      q[e] = __hip_fp8_e4m3(fminf(fmaxf(v[e] * inv, -448.f), 448.f)).__x;
+      q[e] = quant_e4m3(v[e], s);
     if constexpr (VEC == 8) {
       *reinterpret_cast<uint2*>(dst + base) =
           *reinterpret_cast<const uint2*>(q);
@@ -31,9 +41,7 @@ __global__ void quantize_e4m3_kernel(const T* __restrict__ src,
           *reinterpret_cast<const unsigned int*>(q);
     }
   } else {
-    for (long i = base; i < n; ++i)
-      dst[i] = __hip_fp8_e4m3(
-          fminf(fmaxf(ld(src + i) / scale[0], -448.f), 448.f)).__x;
+    for (long i = base; i < n; ++i) dst[i] = quant_e4m3(ld(src + i), s);
   }
 }
 
