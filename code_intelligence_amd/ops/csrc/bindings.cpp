@@ -30,6 +30,11 @@ void lstm_seq_backward(at::Tensor dhs, at::Tensor dhT, at::Tensor dcT,
                        at::Tensor c0, at::Tensor w_hh, at::Tensor dgates,
                        at::Tensor dh0, at::Tensor dc0, bool need_dh0);
 at::Tensor concat_pool(at::Tensor hidden, at::Tensor lengths);
+std::vector<at::Tensor> concat_pool_fwd_idx(at::Tensor hidden,
+                                            at::Tensor lengths, long max_len);
+at::Tensor concat_pool_bwd(at::Tensor dout, at::Tensor argmax,
+                           at::Tensor lengths, long max_len,
+                           at::Tensor like_hidden);
 std::vector<at::Tensor> qrnn_fo_pool_fwd(at::Tensor gates, at::Tensor c0);
 std::vector<at::Tensor> qrnn_fo_pool_bwd(at::Tensor gates, at::Tensor c,
                                          at::Tensor c0, at::Tensor dh,
@@ -84,6 +89,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dgates"), py::arg("dh0"), py::arg("dc0"),
         py::arg("need_dh0") = true);
   m.def("concat_pool", &ci::concat_pool, "masked mean/max/last concat pool");
+  m.def("concat_pool_fwd_idx", &ci::concat_pool_fwd_idx,
+        "windowed strided concat pool -> (out, argmax); max_len <= 0: no window");
+  m.def("concat_pool_bwd", &ci::concat_pool_bwd,
+        "concat pool backward: dhidden laid out like like_hidden");
   m.def("qrnn_fo_pool_fwd", &ci::qrnn_fo_pool_fwd,
         "QRNN fo-pool forward scan (activates gates in place)");
   m.def("qrnn_fo_pool_bwd", &ci::qrnn_fo_pool_bwd,

@@ -244,8 +244,9 @@ class _FusedLSTMFunction(torch.autograd.Function):
         if T > 1:
             dw_hh += torch.mm(dgates[1:].reshape((T - 1) * B, 4 * H).t(),
                               hs[:-1].reshape((T - 1) * B, H))
-        if _side_dw_enabled():
+        if _side_dw_enabled() and ctx.needs_input_grad[3]:
             # overlap dW_ih/db with the next layer's sequential loop
+            # (never for a frozen layer: its .grad must stay None)
             pw, pbi, pbh = ctx.direct_params
             s_ = _side()
             s_.wait_stream(torch.cuda.current_stream())

@@ -1,0 +1,114 @@
+"""Classifier fine-tune CLI — the schedule of the reference's
+Issue_Embeddings/notebooks/06_FineTune.ipynb on an encoder artifact:
+
+    freeze();       fit_one_cycle(3, max_lr=.1)
+                    fit(1, lr=slice(4e-4))
+    freeze_to(-2);  fit(1, lr=slice(1e-4))
+                    fit(1, lr=slice(4e-4))
+
+``--artifacts`` is the directory ``engine.inference.save_artifacts`` writes
+(config.json + vocab.json + encoder.pth); ``--data`` is a JSONL file of
+``{"text": ..., "labels": [...]}`` rows (multi-label, like the notebook).
+
+Usage: python -m code_intelligence_amd.train.finetune_cli \
+           --artifacts model_files/lm --data issues.jsonl --out clas.pth
+"""
+from __future__ import annotations
+
+import argparse
+import json
+from pathlib import Path
+
+import torch
+
+from ..models.awd_lstm import awd_lstm_lm_config
+from ..models.classifier import get_text_classifier
+from ..text.tokenizer import Tokenizer, Vocab
+from .classifier import ClassifierTrainer, PaddedBatchLoader
+
+
+def build_argparser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description=__doc__)
+    p.add_argument("--artifacts", type=str, required=True)
+    p.add_argument("--data", type=str, required=True)
+    p.add_argument("--out", type=str, default=None,
+                   help="write the trainer checkpoint + label list here")
+    p.add_argument("--bs", type=int, default=32)
+    p.add_argument("--bptt", type=int, default=70)
+    p.add_argument("--max_len", type=int, default=1400)
+    p.add_argument("--valid_pct", type=float, default=0.1)
+    p.add_argument("--dtype", type=str, default="bf16", choices=["bf16", "fp32"])
+    p.add_argument("--device", type=str, default=None)
+    p.add_argument("--seed", type=int, default=42)
+    return p
+
+
+def load_rows(path, tokenizer: Tokenizer, vocab: Vocab):
+    """JSONL -> (token id lists, multi-hot label matrix, label names)."""
+    rows = [json.loads(l) for l in Path(path).read_text().splitlines() if l.strip()]
+    names = sorted({lab for r in rows for lab in r["labels"]})
+    index = {n: i for i, n in enumerate(names)}
+    docs = [vocab.numericalize(tokenizer.process_text(r["text"])) for r in rows]
+    y = torch.zeros(len(rows), len(names))
+    for i, r in enumerate(rows):
+        for lab in r["labels"]:
+            y[i, index[lab]] = 1.0
+    return docs, y, names
+
+
+def main(argv=None) -> dict:
+    args = build_argparser().parse_args(argv)
+    torch.manual_seed(args.seed)
+    device = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
+    root = Path(args.artifacts)
+    art = json.loads((root / "config.json").read_text())
+    vocab = Vocab.load(root / "vocab.json")
+    docs, y, names = load_rows(args.data, Tokenizer(), vocab)
+
+    # like the notebook: the LM config, sized as the encoder was trained
+    config = dict(awd_lstm_lm_config)
+    config.update(emb_sz=art["emb_sz"], n_hid=art["n_hid"],
+                  n_layers=art["n_layers"], qrnn=art.get("qrnn", False))
+    model = get_text_classifier(len(vocab), len(names), bptt=args.bptt,
+                                max_len=args.max_len, config=config)
+    model.load_encoder(root / art.get("encoder_file", "encoder.pth"))
+    dtype = torch.bfloat16 if (args.dtype == "bf16" and device != "cpu") \
+        else torch.float32
+    model = model.to(device=device, dtype=dtype)
+
+    n_valid = int(len(docs) * args.valid_pct)
+    perm = torch.randperm(len(docs)).tolist()
+    va, tr = perm[:n_valid], perm[n_valid:]
+    pad = model.encoder.pad_token
+    train = PaddedBatchLoader([docs[i] for i in tr], y[tr], args.bs, pad,
+                              device=device, seed=args.seed, drop_last=True)
+    valid = PaddedBatchLoader([docs[i] for i in va], y[va], args.bs, pad,
+                              device=device, shuffle=False) if va else None
+
+    trainer = ClassifierTrainer(model, multi_label=True)
+    history = []
+
+    def stage(name, fn, *a):
+        losses = fn(train, *a)
+        rec = {"stage": name, "train_loss": sum(losses) / max(len(losses), 1)}
+        if valid is not None:
+            rec.update(trainer.evaluate(valid))
+        history.append(rec)
+        print(json.dumps(rec))
+
+    trainer.freeze()
+    stage("frozen one_cycle(3, .1)", trainer.fit_one_cycle, 3, 0.1)
+    stage("frozen fit(1, slice(4e-4))", trainer.fit, 1, slice(4e-4))
+    trainer.freeze_to(-2)
+    stage("freeze_to(-2) fit(1, slice(1e-4))", trainer.fit, 1, slice(1e-4))
+    stage("freeze_to(-2) fit(1, slice(4e-4))", trainer.fit, 1, slice(4e-4))
+    if args.out:
+        trainer.save(args.out)
+        Path(str(args.out) + ".labels.json").write_text(json.dumps(names))
+    result = {"final": history[-1], "labels": len(names)}
+    print(json.dumps(result))
+    return result
+
+
+if __name__ == "__main__":
+    main()
