@@ -90,6 +90,32 @@ def _ce_overlap_enabled() -> bool:
     return os.environ.get("CI_CE_2STREAM", "0") == "1"
 
 
+def _h_aug_t(lib, h: Tensor, has_bias: bool) -> Tensor:
+    """(Haug, N) K-major copy of the decoder input for the dW GEMM, built
+    once per backward by the pack kernel (kmajor_pack.hip).
+    mm(dlog.t(), h[s:e]) hands the library a GEMM with both operands
+    strided along the reduction (the chunk's rows); mm(hT[:, s:e], dlog) is
+    a plain row-major one: 8.44 -> 7.20 ms per 65536-row chunk at V = 60000
+    (profiles/BENCH_HISTORY.md). With a bias, row H is ones and rows
+    H+1..H+15 are zero padding."""
+    N, H = h.shape
+    Haug = H + 16 if has_bias else H
+    h_augT = torch.empty(Haug, N, dtype=h.dtype, device=h.device)
+    lib.pack_kmajor(h.detach().contiguous(), h_augT, 0, 0)
+    if has_bias:
+        h_augT[H] = 1
+        h_augT[H + 1:] = 0
+    return h_augT
+
+
+def _split_dw_aug_t(lib, dw_augT: Tensor, H: int, has_bias: bool):
+    """fp32 (Haug, V) sums -> dw (V, H) contiguous fp32, db (V,) or None."""
+    dw = torch.empty(dw_augT.shape[1], H, dtype=dw_augT.dtype,
+                     device=dw_augT.device)
+    lib.pack_kmajor(dw_augT[:H], dw, 0, 0)
+    return dw, (dw_augT[H] if has_bias else None)
+
+
 class _FusedCEFp8Function(torch.autograd.Function):
     """fp8-GEMM variant of the fused tied-decoder CE (see _fp8r_enabled).
     Loss/grad parity vs the bf16 path is locked by
@@ -205,17 +231,13 @@ class _FusedCEFp8Function(torch.autograd.Function):
         sc_over_store = (scale.reshape(()) / _STORE)
         scratch8 = None if onepass else \
             torch.empty(min(C, N), V, dtype=f8, device=dev)
-        # db folded into the dW GEMM: h gains a 16-column pad whose first
-        # extra column is ones, so column H of dW_aug IS sum(dlog) — the
+        # db folded into the dW GEMM: h^T gains a 16-row pad whose first
+        # extra row is ones, so row H of dW_aug^T IS sum(dlog) — the
         # separate db reduction re-read the whole dlog chunk (7.9 GB at
-        # the bench shape); 16 (not 1) keeps the GEMM N%16 alignment
-        Haug = H + 16 if has_bias else H
-        h_aug = h
-        if has_bias:
-            h_aug = torch.zeros(N, Haug, dtype=h.dtype, device=dev)
-            h_aug[:, :H] = h
-            h_aug[:, H] = 1
-        dw_aug = torch.zeros(V, Haug, dtype=torch.float32, device=dev)
+        # the bench shape); 16 (not 1) keeps the GEMM M%16 alignment
+        h_augT = _h_aug_t(lib, h, has_bias)
+        dw_augT = torch.zeros(h_augT.shape[0], V, dtype=torch.float32,
+                              device=dev)
         recompute = None if logits_full is not None else \
             torch.empty(min(C, N), V, dtype=h.dtype, device=dev)
         # (V, H) column-major e4m3 weight for the fp8 dh GEMM
@@ -259,13 +281,12 @@ class _FusedCEFp8Function(torch.autograd.Function):
                 # epilogue + dh (disjoint slices of the resident buffer)
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
-                    dw_aug += torch.mm(dlog.t(), h_aug[s:e])
+                    dw_augT += torch.mm(h_augT[:, s:e], dlog)
             else:
-                dw_aug += torch.mm(dlog.t(), h_aug[s:e])
+                dw_augT += torch.mm(h_augT[:, s:e], dlog)
         if overlap:
             main.wait_stream(side)
-        dw = dw_aug[:, :H]
-        db = dw_aug[:, H] if has_bias else None
+        dw, db = _split_dw_aug_t(lib, dw_augT, H, has_bias)
         if onepass:
             # the stored bf16 dlogits carry 1/N, not dloss/N: apply dloss
             # to the fp32 sums inside the casts that run anyway (x*1 is
@@ -332,15 +353,11 @@ class _FusedCEFunction(torch.autograd.Function):
             torch.empty(min(C, N), V, dtype=h.dtype, device=h.device)
         w_t = weight.t()
         bias_arg = b32 if has_bias else _empty_f32(h.device)
-        # db folded into the dW GEMM via a ones-column (see the fp8
-        # variant above for the rationale and the 16-column alignment pad)
-        Haug = H + 16 if has_bias else H
-        h_aug = h
-        if has_bias:
-            h_aug = torch.zeros(N, Haug, dtype=h.dtype, device=h.device)
-            h_aug[:, :H] = h
-            h_aug[:, H] = 1
-        dw_aug = torch.zeros(V, Haug, dtype=torch.float32, device=h.device)
+        # db folded into the dW GEMM via a ones-row (see the fp8
+        # variant above for the rationale and the 16-row alignment pad)
+        h_augT = _h_aug_t(lib, h, has_bias)
+        dw_augT = torch.zeros(h_augT.shape[0], V, dtype=torch.float32,
+                              device=h.device)
         for s in range(0, N, C):
             e = min(N, s + C)
             if logits_full is not None:
@@ -351,9 +368,8 @@ class _FusedCEFunction(torch.autograd.Function):
             # in-place: dlog <- (softmax(dlog + bias) - onehot) * scale
             lib.ce_dlogits(dlog, targets[s:e], bias_arg, lse[s:e], scale)
             torch.mm(dlog, weight, out=dh[s:e])
-            dw_aug += torch.mm(dlog.t(), h_aug[s:e])
-        dw = dw_aug[:, :H]
-        db = dw_aug[:, H] if has_bias else None
+            dw_augT += torch.mm(h_augT[:, s:e], dlog)
+        dw, db = _split_dw_aug_t(lib, dw_augT, H, has_bias)
         return (dh, dw.to(weight.dtype),
                 db.to(ctx.bias_dtype) if has_bias else None, None)
 

@@ -1,6 +1,7 @@
 // Python bindings for the code_intelligence_amd gfx950 kernels.
 #include <torch/extension.h>
 #include <string>
+#include <tuple>
 #include <vector>
 
 namespace ci {
@@ -64,6 +65,10 @@ at::Tensor emb_scatter(at::Tensor gout, at::Tensor ids, at::Tensor rowmask,
                        long V, long pad_idx);
 at::Tensor dropconnect_apply(at::Tensor w, long seed, double p);
 void dropconnect_grad_(at::Tensor g, long seed, double p);
+void pack_kmajor(at::Tensor src, at::Tensor dst, long row_off, long col_off);
+std::tuple<at::Tensor, at::Tensor> lstm_weight_grads(
+    at::Tensor dgates, at::Tensor x_tm, at::Tensor hs, at::Tensor h0,
+    bool need_ih, bool need_hh);
 }  // namespace ci
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -117,4 +122,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "seeded DropConnect mask-scale (no mask tensor)");
   m.def("dropconnect_grad_", &ci::dropconnect_grad_,
         "in-place seeded DropConnect grad mask");
+  m.def("pack_kmajor", &ci::pack_kmajor,
+        "dst[row_off + c, col_off + r] = src[r, c] (tiled LDS transpose)",
+        py::arg("src"), py::arg("dst"), py::arg("row_off") = 0,
+        py::arg("col_off") = 0);
+  m.def("lstm_weight_grads", &ci::lstm_weight_grads,
+        "LSTM dW_ih/dW_hh: K-major pack of [x ; h_prev] + one NN GEMM",
+        py::arg("dgates"), py::arg("x_tm"), py::arg("hs"), py::arg("h0"),
+        py::arg("need_ih") = true, py::arg("need_hh") = true);
 }

@@ -39,6 +39,7 @@ SOURCES = [
     "dropconnect.hip",
     "artar.hip",
     "fp8util.hip",
+    "kmajor_pack.hip",
     "tokenizer.cpp",
 ]
 

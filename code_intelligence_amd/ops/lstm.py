@@ -115,6 +115,41 @@ def _q8(lib, t: Tensor):
     return q, scale
 
 
+def _kmajor_dw(T: int, B: int, In: int, H: int, dt) -> bool:
+    """Weight gradients through lstm_weight_grads (kmajor_pack.hip)?
+
+    torch.mm(dg.t(), x) gives the library a GEMM with BOTH operands strided
+    along K = T*B; with [x ; h_prev] packed K-major it runs one plain NN GEMM
+    per layer instead (measured at T*B = 262144, profiles/BENCH_HISTORY.md:
+    34.9 -> 27.7 ms at In = H = 2400 including the pack). The stacked GEMM's
+    (In+H, 4H) output must still give every CU a 256x256 tile: below that
+    the library's default choice for the new shape loses to the three tuned
+    GEMMs (In=2400, H=800: 156 tiles, 8.8 vs 7.3 ms), which then stay.
+    CI_LSTM_DW=legacy restores the three-GEMM form everywhere (A/B runs)."""
+    if os.environ.get("CI_LSTM_DW", "") == "legacy":
+        return False
+    if dt not in (torch.bfloat16, torch.float32):
+        return False
+    if T * B < _KMAJOR_MIN_K:
+        return True
+    return (In + H) * 4 * H >= 256 * 256 * _n_cus()
+
+
+# below this reduction length neither form is GEMM-bound (a few launches
+# either way), so the tile rule has nothing to decide: small shapes take the
+# same native path as the large layers
+_KMAJOR_MIN_K = 4096
+_cus = None
+
+
+def _n_cus() -> int:
+    global _cus
+    if _cus is None:
+        _cus = torch.cuda.get_device_properties(
+            torch.cuda.current_device()).multi_processor_count
+    return _cus
+
+
 def _cpu_lstm_loop(x: Tensor, h0: Tensor, c0: Tensor, w_ih: Tensor, w_hh: Tensor,
                    b_ih: Tensor, b_hh: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
     """Pure-PyTorch reference (autograd-capable). x: (B,T,In)."""
@@ -238,13 +273,22 @@ class _FusedLSTMFunction(torch.autograd.Function):
         dh0_out = dh0.to(dt) if need_dh0 else None
         dg2 = dgates.view(T * B, 4 * H)
         dx_tm = torch.mm(dg2, w_ih).view(T, B, In)
-        # dW_hh = sum_t h_{t-1}^T dgates_t — time-major slices stay
-        # contiguous, so no (T,B,H) cat materializes:
-        dw_hh = torch.mm(dgates[0].t(), h0.to(dt))
-        if T > 1:
-            dw_hh += torch.mm(dgates[1:].reshape((T - 1) * B, 4 * H).t(),
-                              hs[:-1].reshape((T - 1) * B, H))
-        if _side_dw_enabled() and ctx.needs_input_grad[3]:
+        need_ih, need_hh = ctx.needs_input_grad[3], ctx.needs_input_grad[4]
+        side = _side_dw_enabled() and need_ih
+        if side or not _kmajor_dw(T, B, In, H, dt):
+            # dW_hh = sum_t h_{t-1}^T dgates_t — time-major slices stay
+            # contiguous, so no (T,B,H) cat materializes:
+            dw_hh = torch.mm(dgates[0].t(), h0.to(dt))
+            if T > 1:
+                dw_hh += torch.mm(dgates[1:].reshape((T - 1) * B, 4 * H).t(),
+                                  hs[:-1].reshape((T - 1) * B, H))
+            dw_ih = None
+        else:
+            # [x ; h_prev] written K-major once, then ONE row-major GEMM per
+            # layer instead of three with both operands strided along K
+            dw_ih, dw_hh = lib.lstm_weight_grads(dgates, x_tm, hs, h0.to(dt),
+                                                 need_ih, need_hh)
+        if side:
             # overlap dW_ih/db with the next layer's sequential loop
             # (never for a frozen layer: its .grad must stay None)
             pw, pbi, pbh = ctx.direct_params
@@ -262,10 +306,13 @@ class _FusedLSTMFunction(torch.autograd.Function):
                 _accum_grad(pbh, db_s.clone())
             return (dx_tm.transpose(0, 1), dh0_out, dc0.to(dt),
                     None, dw_hh.to(w_hh.dtype), None, None)
-        dw_ih = torch.mm(dg2.t(), x_tm.view(T * B, In))
+        if dw_ih is None and need_ih:
+            dw_ih = torch.mm(dg2.t(), x_tm.view(T * B, In))
         db = dg2.sum(dim=0).to(dt)
         return (dx_tm.transpose(0, 1), dh0_out, dc0.to(dt),
-                dw_ih.to(w_ih.dtype), dw_hh.to(w_hh.dtype), db, db.clone())
+                dw_ih.to(w_ih.dtype) if dw_ih is not None else None,
+                dw_hh.to(w_hh.dtype) if dw_hh is not None else None,
+                db, db.clone())
 
 
 def lstm_forward(x: Tensor, h0: Tensor, c0: Tensor, w_ih: Tensor, w_hh: Tensor,
