@@ -1,7 +1,10 @@
 """Model registry/dispatcher (reference: issue_label_predictor.py).
 
 Always loads the universal model; loads per-org and per-repo combined
-models from the MODEL_CONFIG yaml (env, populated by a configmap in the
+models (kinds ``automl``, ``repo_specific`` and ``finetuned_classifier``: an
+artifact directory ``path``, ``org``, optionally ``repo`` and optionally a
+torch ``device`` string, default: the GPU when there is one) from the
+MODEL_CONFIG yaml (env, populated by a configmap in the
 reference — issue_label_predictor.py:63-71); routes an issue to the best
 model: '{org}/{repo}_combined' > '{org}_combined' > 'universal'
 (146-155); ``predict(payload)`` dispatches on payload keys (183-227)."""
@@ -73,6 +76,10 @@ class IssueLabelPredictor:
                 raise ValueError(f"repo_specific spec needs 'repo': {spec}")
             m = RepoSpecificLabelModel.from_repo(
                 org, repo, embedding_api_endpoint=self.embedding_api_endpoint)
+        elif kind == "finetuned_classifier":
+            from .finetuned_classifier_model import FineTunedClassifierLabelModel
+            m = FineTunedClassifierLabelModel.from_path(
+                spec["path"], device=spec.get("device"))
         else:
             raise ValueError(f"unknown model kind {kind}")
         key = f"{org}/{repo}_combined" if repo else f"{org}_combined"

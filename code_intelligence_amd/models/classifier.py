@@ -20,13 +20,15 @@ and ``1.layers.{0,2,4,6}.*`` and ``save_encoder`` artifacts load into
 """
 from __future__ import annotations
 
+import weakref
 from itertools import chain
 from typing import List, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor, nn
 
-from ..ops.pool import concat_pool
+from ..ops.pool import (StreamingConcatPool, concat_pool, head_fits_lds,
+                        pool_head)
 from .awd_lstm import AWDLSTMEncoder
 
 __all__ = [
@@ -79,6 +81,7 @@ class MultiBatchEncoder(nn.Module):
         self.module = encoder
         self.bptt, self.max_len = bptt, max_len
         self.kept_chunks = 0  # of the last forward (introspection/tests)
+        self.max_live_chunks = 0  # most chunks seen alive at once, last stream_pool
 
     def reset(self, bs: Optional[int] = None) -> None:
         self.module.reset(bs)
@@ -106,6 +109,43 @@ class MultiBatchEncoder(nn.Module):
         self.kept_chunks = len(kept)
         hidden_tm = kept[0] if len(kept) == 1 else torch.cat(kept, dim=0)
         return hidden_tm.transpose(0, 1), lens - start
+
+    @torch.no_grad()
+    def stream_pool(self, ids: Tensor, lengths: Tensor,
+                    dtype: torch.dtype = torch.float32) -> StreamingConcatPool:
+        """Inference-only walk: the chunks, reset, length clamp and skipped
+        prefix of ``forward``, but every chunk is folded into a
+        ``StreamingConcatPool`` and dropped before the next encoder call, so
+        one chunk of hidden states is alive at a time whatever the document
+        length. ``max_live_chunks`` records what was observed: 1 plus whether
+        the previous chunk's final-layer tensor was still referenced when an
+        encoder call started. Returns the pool (absolute lengths, ``max_len``
+        window)."""
+        B, T = ids.shape
+        lens = lengths.to(ids.device).clamp(1, T)
+        g = int((lens - self.max_len).clamp_min(0).min())
+        self.module.reset(B)
+        pool = StreamingConcatPool(B, self.module.emb_sz, self.max_len,
+                                   ids.device, dtype)
+        lens_p = lens.to(torch.int32) if ids.is_cuda else lens
+        self.max_live_chunks = 0
+        prev = None     # weak reference to the previous chunk's final states
+        for s in range(0, T, self.bptt):
+            e = min(s + self.bptt, T)
+            if e <= g:
+                self.module(ids[:, s:e])
+                continue
+            # observed, not assumed: is the previous chunk's tensor still
+            # referenced anywhere as the next encoder call starts?
+            carried = int(prev is not None and prev() is not None)
+            # bind the final layer's states only: the encoder's two per-layer
+            # lists die with this expression
+            h = self.module(ids[:, s:e])[1][-1]
+            self.max_live_chunks = max(self.max_live_chunks, carried + 1)
+            pool.update(h, lens_p, s)
+            prev = weakref.ref(h)
+            del h
+        return pool
 
 
 class PoolingLinearClassifier(nn.Module):
@@ -138,6 +178,38 @@ class PoolingLinearClassifier(nn.Module):
         return self.layers(pooled)
 
 
+@torch.no_grad()
+def fold_head_bn(head: PoolingLinearClassifier
+                 ) -> Optional[Tuple[Tensor, Tensor, Tensor, Tensor]]:
+    """Fold the eval-mode BatchNorms of the standard head into its Linears.
+
+    Accepts exactly ``BatchNorm1d, Dropout, Linear, ReLU, BatchNorm1d,
+    Dropout, Linear`` (``None`` for anything else). With s = gamma /
+    sqrt(var + eps) and t = beta - mean * s, ``Linear(BN(x))`` is
+    ``(W * s) x + (W t + b)``; the fold runs in fp64 and is rounded to fp32
+    once. Returns ``(w1, b1, w2, b2)``."""
+    mods = list(head.layers)
+    kinds = (nn.BatchNorm1d, nn.Dropout, nn.Linear, nn.ReLU,
+             nn.BatchNorm1d, nn.Dropout, nn.Linear)
+    if len(mods) != len(kinds) or not all(
+            type(m) is k for m, k in zip(mods, kinds)):
+        return None
+    out: List[Tensor] = []
+    for bn, lin in ((mods[0], mods[2]), (mods[4], mods[6])):
+        if bn.running_mean is None or bn.running_var is None:
+            return None
+        s = (bn.running_var.double() + bn.eps).rsqrt()
+        t = -bn.running_mean.double() * s
+        if bn.affine:
+            s, t = s * bn.weight.double(), t * bn.weight.double() + bn.bias.double()
+        w = lin.weight.double()
+        b = w @ t
+        if lin.bias is not None:
+            b = b + lin.bias.double()
+        out += [(w * s).float().contiguous(), b.float().contiguous()]
+    return out[0], out[1], out[2], out[3]
+
+
 class TextClassifier(nn.Sequential):
     """``[0]`` MultiBatchEncoder (encoder under ``.module``), ``[1]`` head."""
 
@@ -161,6 +233,64 @@ class TextClassifier(nn.Sequential):
         hidden, lens = self[0](ids, lengths)
         pooled = concat_pool(hidden, lens, self[0].max_len)
         return self[1](pooled.float())
+
+    # --- inference ---------------------------------------------------------
+    _folded: Optional[Tuple[Tensor, Tensor, Tensor, Tensor]] = None
+    _fold_tried = False
+
+    def train(self, mode: bool = True):
+        if mode:
+            self._folded, self._fold_tried = None, False
+        return super().train(mode)
+
+    def load_state_dict(self, *args, **kwargs):
+        self._folded, self._fold_tried = None, False
+        return super().load_state_dict(*args, **kwargs)
+
+    def _apply(self, fn, *args, **kwargs):
+        self._folded, self._fold_tried = None, False
+        return super()._apply(fn, *args, **kwargs)
+
+    def _folded_head(self) -> Optional[Tuple[Tensor, Tensor, Tensor, Tensor]]:
+        """Cached ``fold_head_bn(self.head)``; dropped by ``train()``,
+        ``load_state_dict`` and device/dtype moves. Parameters edited in
+        place while the model stays in eval mode are not noticed."""
+        if not self._fold_tried:
+            self._folded, self._fold_tried = fold_head_bn(self.head), True
+        return self._folded
+
+    def predict_proba(self, ids: Tensor, lengths: Tensor,
+                      multi_label: bool = True) -> Tuple[Tensor, Tensor]:
+        """ids (B,T) end-padded, lengths (B,) -> (probs, logits), fp32 (B, C).
+
+        Every module is put in eval mode and ``no_grad`` holds for the call;
+        afterwards each module gets its own training flag back (frozen groups
+        that were in eval under a training root stay in eval). The document
+        is streamed through ``stream_pool``; the standard one-hidden-layer
+        head then runs BatchNorm-folded in one fused launch, any other head
+        as ``self.head`` on the streamed features."""
+        flags = [(m, m.training) for m in self.modules()]
+        if any(f for _, f in flags):
+            # something was training: its weights or BatchNorm statistics
+            # may have moved since the head was last folded
+            self._folded, self._fold_tried = None, False
+            for m, _ in flags:
+                m.training = False
+        try:
+            with torch.no_grad():
+                pool = self[0].stream_pool(ids, lengths)
+                folded = self._folded_head()
+                if folded is not None and head_fits_lds(
+                        pool.H, folded[0].size(0), folded[2].size(0)):
+                    return pool_head(pool.state, pool.lengths, pool.max_len,
+                                     *folded, multi_label=multi_label)
+                logits = self[1](pool.features().float())
+                probs = torch.sigmoid(logits) if multi_label \
+                    else torch.softmax(logits, dim=1)
+                return probs, logits
+        finally:
+            for m, f in flags:
+                m.training = f
 
     def load_encoder(self, path, map_location="cpu") -> None:
         """Load what ``AWDLSTM.save_encoder`` / fastai ``save_encoder`` wrote."""

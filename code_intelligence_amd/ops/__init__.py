@@ -3,12 +3,13 @@ pure-PyTorch CPU reference implementations. See SURVEY.md §2.4 for the
 kernel inventory (K1-K9)."""
 from . import extension
 from .lstm import lstm_forward
-from .pool import concat_pool
+from .pool import concat_pool, StreamingConcatPool, pool_head
 from .dropout import variational_dropout
 from .crossentropy import tied_decoder_ce, TiedDecoderCE
 from .adam import FusedAdamW
 
 __all__ = [
-    "extension", "lstm_forward", "concat_pool", "variational_dropout",
+    "extension", "lstm_forward", "concat_pool", "StreamingConcatPool",
+    "pool_head", "variational_dropout",
     "tied_decoder_ce", "TiedDecoderCE", "FusedAdamW",
 ]

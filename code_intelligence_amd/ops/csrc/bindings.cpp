@@ -36,6 +36,12 @@ std::vector<at::Tensor> concat_pool_fwd_idx(at::Tensor hidden,
 at::Tensor concat_pool_bwd(at::Tensor dout, at::Tensor argmax,
                            at::Tensor lengths, long max_len,
                            at::Tensor like_hidden);
+void concat_pool_accum(at::Tensor state, at::Tensor hidden,
+                       at::Tensor lengths, long t0, long max_len);
+std::vector<at::Tensor> pool_head_fwd(at::Tensor state, at::Tensor lengths,
+                                      long max_len, at::Tensor w1,
+                                      at::Tensor b1, at::Tensor w2,
+                                      at::Tensor b2, bool multi_label);
 std::vector<at::Tensor> qrnn_fo_pool_fwd(at::Tensor gates, at::Tensor c0);
 std::vector<at::Tensor> qrnn_fo_pool_bwd(at::Tensor gates, at::Tensor c,
                                          at::Tensor c0, at::Tensor dh,
@@ -98,6 +104,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "windowed strided concat pool -> (out, argmax); max_len <= 0: no window");
   m.def("concat_pool_bwd", &ci::concat_pool_bwd,
         "concat pool backward: dhidden laid out like like_hidden");
+  m.def("concat_pool_accum", &ci::concat_pool_accum,
+        "fold one (B,Tc,H) chunk into the fp32 [sum|max|last] pool state",
+        py::arg("state"), py::arg("hidden"), py::arg("lengths"),
+        py::arg("t0"), py::arg("max_len"));
+  m.def("pool_head_fwd", &ci::pool_head_fwd,
+        "finalise the pool state + BN-folded two-layer head -> (probs, logits)",
+        py::arg("state"), py::arg("lengths"), py::arg("max_len"),
+        py::arg("w1"), py::arg("b1"), py::arg("w2"), py::arg("b2"),
+        py::arg("multi_label"));
   m.def("qrnn_fo_pool_fwd", &ci::qrnn_fo_pool_fwd,
         "QRNN fo-pool forward scan (activates gates in place)");
   m.def("qrnn_fo_pool_bwd", &ci::qrnn_fo_pool_bwd,

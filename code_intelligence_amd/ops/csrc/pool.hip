@@ -2,6 +2,7 @@
 // Single-pass reduction over T; reference semantics inference.py:232-263
 // (batch_seq_pool: padding masked per true length; "last" = h[length-1]).
 #include "common.h"
+#include "pool_tile.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -60,25 +61,9 @@ at::Tensor concat_pool(at::Tensor hidden, at::Tensor lengths) {
 // contiguous batch-major tensor and the (B,T,H) transpose view of the LSTM's
 // native (T,B,H) storage are read in place (artar.hip does the same for raw).
 //
-// Thread map (both kernels): a 256-thread block is HL h-lanes x TS t-slices;
-// consecutive lanes own consecutive 16-B packets of h (VEC = 16/sizeof(T), or
-// VEC = 1 scalars when H or a stride is not packet-aligned), so every access
-// is a run of HL*16 contiguous bytes in either layout. B*H/VEC alone is only
-// ~3k lanes at the fine-tune shape (32 x 800 bf16), far too few to cover HBM
-// latency, so the T loop is split over the TS slices of a block (forward:
-// combined through LDS in a fixed order, so results are deterministic) and,
-// in backward, additionally over blockIdx.z.
-template <int VEC> struct PoolTile {
-  static constexpr int HL = VEC == 1 ? 64 : 16;  // h lanes per block
-  static constexpr int TS = 256 / HL;            // t slices per block
-};
-
-static __device__ __forceinline__ void pool_window(const int* lengths, int b,
-                                                   int Tn, int max_len,
-                                                   int& lo, int& len) {
-  len = min(max(lengths[b], 1), Tn);
-  lo = max_len > 0 ? max(0, len - max_len) : 0;
-}
+// Thread map (both kernels): PoolTile in pool_tile.h. The forward combines
+// its t slices through LDS in a fixed order, so results are deterministic;
+// the backward additionally splits T over blockIdx.z.
 
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void concat_pool_fwd_idx_kernel(
@@ -189,14 +174,6 @@ __global__ __launch_bounds__(256) void concat_pool_bwd_kernel(
     }
     stv<T, VEC>(row + (long)t * st, g);
   }
-}
-
-// 16-B packets need every packet start 16-B aligned in both tensors
-template <typename T>
-static bool pool_can_vec(const void* p, int H, long sb, long st) {
-  constexpr int VEC = 16 / sizeof(T);
-  return H % VEC == 0 && sb % VEC == 0 && st % VEC == 0 &&
-         reinterpret_cast<uintptr_t>(p) % 16 == 0;
 }
 
 static void pool_check_hidden(const at::Tensor& hidden,

@@ -32,6 +32,7 @@ SOURCES = [
     "lstm_gemm.hip",
     "lstm_gemv.hip",
     "pool.hip",
+    "pool_stream.hip",
     "qrnn_pool.hip",
     "adam.hip",
     "ce.hip",

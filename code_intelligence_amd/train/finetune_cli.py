@@ -11,7 +11,8 @@ Issue_Embeddings/notebooks/06_FineTune.ipynb on an encoder artifact:
 ``{"text": ..., "labels": [...]}`` rows (multi-label, like the notebook).
 
 Usage: python -m code_intelligence_amd.train.finetune_cli \
-           --artifacts model_files/lm --data issues.jsonl --out clas.pth
+           --artifacts model_files/lm --data issues.jsonl --out clas.pth \
+           [--export_dir model_files/clas]   # ClassifierInferenceWrapper artifact
 """
 from __future__ import annotations
 
@@ -33,6 +34,9 @@ def build_argparser() -> argparse.ArgumentParser:
     p.add_argument("--data", type=str, required=True)
     p.add_argument("--out", type=str, default=None,
                    help="write the trainer checkpoint + label list here")
+    p.add_argument("--export_dir", type=str, default=None,
+                   help="write the serving artifact "
+                        "(engine.classifier_inference) here after the last stage")
     p.add_argument("--bs", type=int, default=32)
     p.add_argument("--bptt", type=int, default=70)
     p.add_argument("--max_len", type=int, default=1400)
@@ -105,6 +109,10 @@ def main(argv=None) -> dict:
     if args.out:
         trainer.save(args.out)
         Path(str(args.out) + ".labels.json").write_text(json.dumps(names))
+    if args.export_dir:
+        from ..engine.classifier_inference import save_classifier_artifacts
+        save_classifier_artifacts(model, vocab, names, args.export_dir,
+                                  multi_label=True)
     result = {"final": history[-1], "labels": len(names)}
     print(json.dumps(result))
     return result
