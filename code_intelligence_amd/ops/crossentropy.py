@@ -25,6 +25,12 @@ e4m3 copy), so backward runs no epilogue pass at all: measured 417.1 vs
 422.1 ms/step (profiles/BENCH_HISTORY.md). Rows wider than the kernel's
 register cache, unaligned shapes and OOM keep the two-kernel path.
 
+Code shape: _FusedCEFunction (bf16/fp32 GEMMs) and _FusedCEFp8Function are
+thin; _ce_forward and _ce_backward own the chunk loop, the resident-or-
+scratch logits buffer, the recompute branch and the dW/db accumulation for
+both. Per chunk they differ only in the logits GEMM (_logits_gemm), the
+epilogue kernel and the dh GEMM; _fp8_chunk is the one eligibility test.
+
 CPU path: plain F.cross_entropy composition (numerics reference)."""
 from __future__ import annotations
 
@@ -73,22 +79,6 @@ _STORE = 448.0  # fixed dlogits store scale: |softmax - onehot| <= 1
 # 16-byte vectors (ce.hip kOnepassMaxVec); wider rows take two kernels
 _ONEPASS_MAX_V = 256 * 32 * 8
 
-_ce_side = None
-
-
-def _ce_side_stream():
-    global _ce_side
-    if _ce_side is None:
-        _ce_side = torch.cuda.Stream()
-    return _ce_side
-
-
-def _ce_overlap_enabled() -> bool:
-    """CI_CE_2STREAM: run each chunk's dW/db GEMMs on a side stream so
-    they overlap the next chunk's dlogits epilogue + fp8 dh GEMM (the two
-    halves touch disjoint chunk slices). Opt-in until measured."""
-    return os.environ.get("CI_CE_2STREAM", "0") == "1"
-
 
 def _h_aug_t(lib, h: Tensor, has_bias: bool) -> Tensor:
     """(Haug, N) K-major copy of the decoder input for the dW GEMM, built
@@ -116,6 +106,186 @@ def _split_dw_aug_t(lib, dw_augT: Tensor, H: int, has_bias: bool):
     return dw, (dw_augT[H] if has_bias else None)
 
 
+def _fp8_chunk(rows: int, H: int, V: int) -> bool:
+    """Whether a chunk of `rows` rows takes the fp8 GEMMs (_scaled_mm wants
+    every dimension a multiple of 16); tail and odd shapes take bf16 ones.
+    Forward, the one-pass decision and backward all ask here: lse belongs
+    to the logits of ONE GEMM, so they must agree chunk by chunk."""
+    return rows % 16 == 0 and H % 16 == 0 and V % 16 == 0
+
+
+def _logits_gemm(out: Tensor, h: Tensor, weight: Tensor, q, s: int, e: int):
+    """out <- h[s:e] @ weight^T. q = (h8, w8, sa, sw), the e4m3 operands and
+    their scales, or None for the all-bf16 path."""
+    if q is not None and _fp8_chunk(e - s, h.shape[1], weight.shape[0]):
+        h8, w8, sa, sw = q
+        # w8.t(): (H, V) column-major view for mat2
+        torch._scaled_mm(h8[s:e], w8.t(), scale_a=sa, scale_b=sw,
+                         out_dtype=h.dtype, out=out)
+    else:
+        torch.mm(h[s:e], weight.t(), out=out)
+
+
+def _try_empty(*shape, dtype, device):
+    try:
+        return torch.empty(*shape, dtype=dtype, device=device)
+    except torch.cuda.OutOfMemoryError:
+        return None
+
+
+def _ce_forward(ctx, h: Tensor, weight: Tensor, bias, targets: Tensor,
+                fp8: bool) -> Tensor:
+    """Chunked forward of both autograd Functions; fp8 picks the GEMMs and
+    the one-pass epilogue (see _fp8r_enabled and the module docstring)."""
+    lib = ext.require()
+    f8 = torch.float8_e4m3fn
+    N, H = h.shape
+    V = weight.shape[0]
+    C = int(os.environ.get("CI_CE_CHUNK", _FusedCEFunction.CHUNK))
+    dev = h.device
+    lse = torch.empty(N, dtype=torch.float32, device=dev)
+    tgt_logit = torch.empty(N, dtype=torch.float32, device=dev)
+    b32 = bias.to(torch.float32) if bias is not None else _empty_f32(dev)
+    tgt64 = targets.to(torch.int64)
+    q = None
+    if fp8:
+        sa = (h.detach().abs().amax().float() / 448.0).clamp_min(1e-12)
+        sw = (weight.detach().abs().amax().float() / 448.0).clamp_min(1e-12)
+        # one-pass quantize kernel (the eager mul+clamp+cast chain is
+        # three kernels and 3x the traffic — fp8util.hip)
+        h8 = torch.empty(h.shape, dtype=f8, device=dev)
+        lib.quantize_e4m3(h.detach().contiguous(), h8, sa)
+        w8 = torch.empty(weight.shape, dtype=f8, device=dev)
+        lib.quantize_e4m3(weight.detach().contiguous(), w8, sw)
+        q = (h8, w8, sa, sw)
+    logits_full = None
+    if os.environ.get("CI_CE_SAVE_LOGITS", "1") != "0":
+        logits_full = _try_empty(N, V, dtype=h.dtype, device=dev)
+    # one-pass epilogue: with a second resident (N, V) e4m3 buffer the
+    # row is read ONCE here (lse + both dlogits forms, scaled 1/N) and
+    # backward runs no epilogue at all. Needs every chunk on the fp8
+    # GEMM path and the row within the kernel's register cache.
+    dlog8_full = None
+    if fp8 and logits_full is not None and V <= _ONEPASS_MAX_V \
+            and all(_fp8_chunk(min(N, s + C) - s, H, V)
+                    for s in range(0, N, C)):
+        dlog8_full = _try_empty(N, V, dtype=f8, device=dev)
+    onepass = dlog8_full is not None
+    if onepass:
+        inv_n = (torch.ones((), dtype=torch.float32, device=dev)
+                 / N).reshape(1)
+    scratch = None if logits_full is not None else \
+        torch.empty(min(C, N), V, dtype=h.dtype, device=dev)
+    for s in range(0, N, C):
+        e = min(N, s + C)
+        logits = logits_full[s:e] if logits_full is not None \
+            else scratch[: e - s]
+        _logits_gemm(logits, h, weight, q, s, e)
+        if onepass:
+            # logits <- bf16((softmax-onehot)/N) in place,
+            # dlog8_full <- e4m3((softmax-onehot)*448), lse out
+            lib.ce_onepass_dual(logits, tgt64[s:e], b32, lse[s:e],
+                                inv_n, dlog8_full[s:e], _STORE)
+        else:
+            lib.ce_rowstats(logits, tgt64[s:e], b32, lse[s:e],
+                            tgt_logit[s:e])
+    if fp8:
+        # exact target logits (bf16 gather-dot, fp32 accumulation): the
+        # loss value must not carry fp8 input-quantization target error
+        wrows = weight.detach()[tgt64]
+        tgt_logit = (h.detach() * wrows).sum(dim=1, dtype=torch.float32)
+        if bias is not None:
+            tgt_logit = tgt_logit + b32[tgt64]
+        # the recompute fallback must rebuild each chunk's logits with the
+        # GEMM that produced them here (lse belongs to THOSE logits), so it
+        # keeps the e4m3 activations: O(N*H) bytes
+        q = (h8 if logits_full is None else None, w8, sa, sw)
+    loss = (lse - tgt_logit).mean()
+    ctx.save_for_backward(h, weight, b32, tgt64, lse)
+    ctx.logits_full = logits_full
+    ctx.dlog8_full = dlog8_full
+    ctx.q = q
+    # backward walks forward's chunks: which GEMM a chunk takes depends on
+    # its size
+    ctx.chunk = C
+    ctx.has_bias = bias is not None
+    ctx.bias_dtype = bias.dtype if bias is not None else None
+    return loss
+
+
+def _ce_backward(ctx, dloss: Tensor):
+    lib = ext.require()
+    h, weight, b32, targets, lse = ctx.saved_tensors
+    # logits_full: forward's logits, or after the one-pass epilogue already
+    # bf16 (softmax-onehot)/N with dlog8_full its e4m3*448 copy
+    logits_full, dlog8_full, q = ctx.logits_full, ctx.dlog8_full, ctx.q
+    ctx.logits_full = ctx.dlog8_full = ctx.q = None  # release asap
+    fp8 = q is not None
+    onepass = dlog8_full is not None
+    has_bias = ctx.has_bias
+    N, H = h.shape
+    V = weight.shape[0]
+    C = ctx.chunk
+    dev = h.device
+    dh = torch.empty_like(h)
+    scale = (dloss / N).to(torch.float32).reshape(1)
+    if fp8:
+        _, w8, _, sw = q
+        sc_over_store = (scale.reshape(()) / _STORE)
+        scratch8 = None if onepass else \
+            torch.empty(min(C, N), V, dtype=torch.float8_e4m3fn, device=dev)
+        # (V, H) column-major e4m3 weight for the fp8 dh GEMM
+        w8_cm = w8.t().contiguous().t()
+    # db folded into the dW GEMM: h^T gains a 16-row pad whose first
+    # extra row is ones, so row H of dW_aug^T IS sum(dlog) — the
+    # separate db reduction re-read the whole dlog chunk (7.9 GB at
+    # the bench shape); 16 (not 1) keeps the GEMM M%16 alignment
+    h_augT = _h_aug_t(lib, h, has_bias)
+    dw_augT = torch.zeros(h_augT.shape[0], V, dtype=torch.float32,
+                          device=dev)
+    recompute = None if logits_full is not None else \
+        torch.empty(min(C, N), V, dtype=h.dtype, device=dev)
+    for s in range(0, N, C):
+        e = min(N, s + C)
+        c = e - s
+        if logits_full is not None:
+            dlog = logits_full[s:e]
+        else:
+            # same GEMM as forward's for this chunk: a bf16 recompute
+            # of fp8-GEMM logits would not match the saved lse
+            dlog = recompute[:c]
+            _logits_gemm(dlog, h, weight, q, s, e)
+        if onepass:
+            dlog8 = dlog8_full[s:e]
+        elif fp8:
+            # dlog <- bf16((softmax-onehot)*dloss/N) in place;
+            # scratch8 <- e4m3((softmax-onehot)*448) in the same read
+            lib.ce_dlogits_dual(dlog, targets[s:e], b32, lse[s:e], scale,
+                                scratch8, _STORE)
+            dlog8 = scratch8[:c]
+        else:
+            # in place: dlog <- (softmax(dlog + bias) - onehot) * scale
+            lib.ce_dlogits(dlog, targets[s:e], b32, lse[s:e], scale)
+        if fp8 and _fp8_chunk(c, H, V):
+            torch._scaled_mm(dlog8, w8_cm, scale_a=sc_over_store,
+                             scale_b=sw, out_dtype=h.dtype, out=dh[s:e])
+        else:
+            torch.mm(dlog, weight, out=dh[s:e])
+        dw_augT += torch.mm(h_augT[:, s:e], dlog)
+    dw, db = _split_dw_aug_t(lib, dw_augT, H, has_bias)
+    if onepass:
+        # the stored bf16 dlogits carry 1/N, not dloss/N: apply dloss
+        # to the fp32 sums inside the casts that run anyway (x*1 is
+        # exact, so dloss == 1 reproduces the two-kernel path's bits)
+        dl = dloss.to(torch.float32)
+        dw_out = torch.empty(V, H, dtype=weight.dtype, device=dev)
+        torch.mul(dw, dl, out=dw_out)
+        return (dh, dw_out,
+                (db * dl).to(ctx.bias_dtype) if has_bias else None, None)
+    return (dh, dw.to(weight.dtype),
+            db.to(ctx.bias_dtype) if has_bias else None, None)
+
+
 class _FusedCEFp8Function(torch.autograd.Function):
     """fp8-GEMM variant of the fused tied-decoder CE (see _fp8r_enabled).
     Loss/grad parity vs the bf16 path is locked by
@@ -125,179 +295,11 @@ class _FusedCEFp8Function(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h: Tensor, weight: Tensor, bias: Tensor, targets: Tensor):
-        lib = ext.require()
-        f8 = torch.float8_e4m3fn
-        N, H = h.shape
-        V = weight.shape[0]
-        C = int(os.environ.get("CI_CE_CHUNK", _FusedCEFunction.CHUNK))
-        dev = h.device
-        lse = torch.empty(N, dtype=torch.float32, device=dev)
-        tgt_logit = torch.empty(N, dtype=torch.float32, device=dev)
-        b32 = bias.to(torch.float32) if bias is not None else _empty_f32(dev)
-        tgt64 = targets.to(torch.int64)
-        sa = (h.detach().abs().amax().float() / 448.0).clamp_min(1e-12)
-        sw = (weight.detach().abs().amax().float() / 448.0).clamp_min(1e-12)
-        # one-pass quantize kernel (the eager mul+clamp+cast chain is
-        # three kernels and 3x the traffic — fp8util.hip)
-        h8 = torch.empty(h.shape, dtype=f8, device=dev)
-        lib.quantize_e4m3(h.detach().contiguous(), h8, sa)
-        w8 = torch.empty(weight.shape, dtype=f8, device=dev)
-        lib.quantize_e4m3(weight.detach().contiguous(), w8, sw)
-        w8_t = w8.t()  # (H, V) column-major view for mat2
-        w_t = weight.t()
-        logits_full = None
-        if os.environ.get("CI_CE_SAVE_LOGITS", "1") != "0":
-            try:
-                logits_full = torch.empty(N, V, dtype=h.dtype, device=dev)
-            except torch.cuda.OutOfMemoryError:
-                pass
-        # one-pass epilogue: with a second resident (N, V) e4m3 buffer the
-        # row is read ONCE here (lse + both dlogits forms, scaled 1/N) and
-        # backward runs no epilogue at all. Needs every chunk on the fp8
-        # GEMM path and the row within the kernel's register cache.
-        dlog8_full = None
-        if logits_full is not None and V <= _ONEPASS_MAX_V \
-                and H % 16 == 0 and V % 16 == 0 \
-                and N % 16 == 0 and min(C, N) % 16 == 0:
-            try:
-                dlog8_full = torch.empty(N, V, dtype=f8, device=dev)
-            except torch.cuda.OutOfMemoryError:
-                pass
-        onepass = dlog8_full is not None
-        if onepass:
-            inv_n = (torch.ones((), dtype=torch.float32, device=dev)
-                     / N).reshape(1)
-        scratch = None if logits_full is not None else \
-            torch.empty(min(C, N), V, dtype=h.dtype, device=dev)
-        for s in range(0, N, C):
-            e = min(N, s + C)
-            logits = logits_full[s:e] if logits_full is not None \
-                else scratch[: e - s]
-            if (e - s) % 16 == 0 and H % 16 == 0 and V % 16 == 0:
-                torch._scaled_mm(h8[s:e], w8_t, scale_a=sa, scale_b=sw,
-                                 out_dtype=h.dtype, out=logits)
-            else:  # tail/odd shapes: bf16 GEMM
-                torch.mm(h[s:e], w_t, out=logits)
-            if onepass:
-                # logits <- bf16((softmax-onehot)/N) in place,
-                # dlog8_full <- e4m3((softmax-onehot)*448), lse out
-                lib.ce_onepass_dual(logits, tgt64[s:e], b32, lse[s:e],
-                                    inv_n, dlog8_full[s:e], _STORE)
-            else:
-                lib.ce_rowstats(logits, tgt64[s:e], b32, lse[s:e],
-                                tgt_logit[s:e])
-        # exact target logits (bf16 gather-dot, fp32 accumulation): the
-        # loss value must not carry fp8 input-quantization target error
-        wrows = weight.detach()[tgt64]
-        tgt_logit = (h.detach() * wrows).sum(dim=1, dtype=torch.float32)
-        if bias is not None:
-            tgt_logit = tgt_logit + b32[tgt64]
-        loss = (lse - tgt_logit).mean()
-        ctx.save_for_backward(h, weight, b32, tgt64, lse, w8, sw)
-        ctx.logits_full = logits_full
-        ctx.dlog8_full = dlog8_full
-        # the recompute fallback must rebuild each chunk's logits with the
-        # GEMM that produced them here (lse belongs to THOSE logits), so it
-        # needs the e4m3 activations and their scale: O(N*H) bytes
-        ctx.h8 = h8 if logits_full is None else None
-        ctx.sa = sa
-        ctx.chunk = C
-        ctx.has_bias = bias is not None
-        ctx.bias_dtype = bias.dtype if bias is not None else None
-        return loss
+        return _ce_forward(ctx, h, weight, bias, targets, fp8=True)
 
     @staticmethod
     def backward(ctx, dloss: Tensor):
-        lib = ext.require()
-        f8 = torch.float8_e4m3fn
-        h, weight, b32, targets, lse, w8, sw = ctx.saved_tensors
-        logits_full = ctx.logits_full
-        ctx.logits_full = None
-        h8, sa = ctx.h8, ctx.sa
-        ctx.h8 = None
-        # set by forward's one-pass epilogue: logits_full already holds
-        # bf16 (softmax-onehot)/N and dlog8_full its e4m3*448 copy
-        dlog8_full = ctx.dlog8_full
-        ctx.dlog8_full = None
-        onepass = dlog8_full is not None
-        has_bias = ctx.has_bias
-        N, H = h.shape
-        V = weight.shape[0]
-        # forward's chunking: which GEMM a chunk takes depends on its size
-        C = ctx.chunk
-        dev = h.device
-        dh = torch.empty_like(h)
-        scale = (dloss / N).to(torch.float32).reshape(1)
-        sc_over_store = (scale.reshape(()) / _STORE)
-        scratch8 = None if onepass else \
-            torch.empty(min(C, N), V, dtype=f8, device=dev)
-        # db folded into the dW GEMM: h^T gains a 16-row pad whose first
-        # extra row is ones, so row H of dW_aug^T IS sum(dlog) — the
-        # separate db reduction re-read the whole dlog chunk (7.9 GB at
-        # the bench shape); 16 (not 1) keeps the GEMM M%16 alignment
-        h_augT = _h_aug_t(lib, h, has_bias)
-        dw_augT = torch.zeros(h_augT.shape[0], V, dtype=torch.float32,
-                              device=dev)
-        recompute = None if logits_full is not None else \
-            torch.empty(min(C, N), V, dtype=h.dtype, device=dev)
-        # (V, H) column-major e4m3 weight for the fp8 dh GEMM
-        w8_cm = w8.t().contiguous().t()
-        w8_t = w8.t()
-        w_t = weight.t()
-        bias_arg = b32 if has_bias else _empty_f32(dev)
-        overlap = _ce_overlap_enabled() and logits_full is not None
-        side = _ce_side_stream() if overlap else None
-        main = torch.cuda.current_stream() if overlap else None
-        for s in range(0, N, C):
-            e = min(N, s + C)
-            c = e - s
-            fp8_chunk = c % 16 == 0 and H % 16 == 0 and V % 16 == 0
-            if logits_full is not None:
-                dlog = logits_full[s:e]
-            else:
-                # same GEMM as forward's for this chunk: a bf16 recompute
-                # of fp8-GEMM logits would not match the saved lse
-                dlog = recompute[:c]
-                if fp8_chunk:
-                    torch._scaled_mm(h8[s:e], w8_t, scale_a=sa, scale_b=sw,
-                                     out_dtype=h.dtype, out=dlog)
-                else:
-                    torch.mm(h[s:e], w_t, out=dlog)
-            if onepass:
-                dlog8 = dlog8_full[s:e]
-            else:
-                # dlog <- bf16((softmax-onehot)*dloss/N) in place;
-                # scratch8 <- e4m3((softmax-onehot)*448) in the same read
-                lib.ce_dlogits_dual(dlog, targets[s:e], bias_arg, lse[s:e],
-                                    scale, scratch8, _STORE)
-                dlog8 = scratch8[:c]
-            if fp8_chunk:
-                torch._scaled_mm(dlog8, w8_cm, scale_a=sc_over_store,
-                                 scale_b=sw, out_dtype=h.dtype, out=dh[s:e])
-            else:
-                torch.mm(dlog, weight, out=dh[s:e])
-            if overlap:
-                # dW(+db) of THIS chunk overlaps the next chunk's
-                # epilogue + dh (disjoint slices of the resident buffer)
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    dw_augT += torch.mm(h_augT[:, s:e], dlog)
-            else:
-                dw_augT += torch.mm(h_augT[:, s:e], dlog)
-        if overlap:
-            main.wait_stream(side)
-        dw, db = _split_dw_aug_t(lib, dw_augT, H, has_bias)
-        if onepass:
-            # the stored bf16 dlogits carry 1/N, not dloss/N: apply dloss
-            # to the fp32 sums inside the casts that run anyway (x*1 is
-            # exact, so dloss == 1 reproduces the two-kernel path's bits)
-            dl = dloss.to(torch.float32)
-            dw_out = torch.empty(V, H, dtype=weight.dtype, device=dev)
-            torch.mul(dw, dl, out=dw_out)
-            return (dh, dw_out,
-                    (db * dl).to(ctx.bias_dtype) if has_bias else None, None)
-        return (dh, dw.to(weight.dtype),
-                db.to(ctx.bias_dtype) if has_bias else None, None)
+        return _ce_backward(ctx, dloss)
 
 
 class _FusedCEFunction(torch.autograd.Function):
@@ -305,73 +307,11 @@ class _FusedCEFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h: Tensor, weight: Tensor, bias: Tensor, targets: Tensor):
-        lib = ext.require()
-        N, H = h.shape
-        V = weight.shape[0]
-        C = int(os.environ.get("CI_CE_CHUNK", _FusedCEFunction.CHUNK))
-        lse = torch.empty(N, dtype=torch.float32, device=h.device)
-        tgt_logit = torch.empty(N, dtype=torch.float32, device=h.device)
-        b32 = bias.to(torch.float32) if bias is not None else _empty_f32(h.device)
-        tgt64 = targets.to(torch.int64)
-        save_logits = os.environ.get("CI_CE_SAVE_LOGITS", "1") != "0"
-        logits_full = None
-        if save_logits:
-            try:
-                logits_full = torch.empty(N, V, dtype=h.dtype, device=h.device)
-            except torch.cuda.OutOfMemoryError:
-                logits_full = None
-        scratch = None if logits_full is not None else \
-            torch.empty(min(C, N), V, dtype=h.dtype, device=h.device)
-        w_t = weight.t()
-        for s in range(0, N, C):
-            e = min(N, s + C)
-            logits = logits_full[s:e] if logits_full is not None \
-                else scratch[: e - s]
-            torch.mm(h[s:e], w_t, out=logits)
-            lib.ce_rowstats(logits, tgt64[s:e], b32, lse[s:e], tgt_logit[s:e])
-        loss = (lse - tgt_logit).mean()
-        ctx.save_for_backward(h, weight, b32, tgt64, lse)
-        ctx.logits_full = logits_full
-        ctx.chunk = C
-        ctx.has_bias = bias is not None
-        ctx.bias_dtype = bias.dtype if bias is not None else None
-        return loss
+        return _ce_forward(ctx, h, weight, bias, targets, fp8=False)
 
     @staticmethod
     def backward(ctx, dloss: Tensor):
-        lib = ext.require()
-        h, weight, b32, targets, lse = ctx.saved_tensors
-        logits_full = ctx.logits_full
-        ctx.logits_full = None  # release asap
-        has_bias = ctx.has_bias
-        N, H = h.shape
-        V = weight.shape[0]
-        C = ctx.chunk
-        dh = torch.empty_like(h)
-        scale = (dloss / N).to(torch.float32).reshape(1)
-        scratch = None if logits_full is not None else \
-            torch.empty(min(C, N), V, dtype=h.dtype, device=h.device)
-        w_t = weight.t()
-        bias_arg = b32 if has_bias else _empty_f32(h.device)
-        # db folded into the dW GEMM via a ones-row (see the fp8
-        # variant above for the rationale and the 16-row alignment pad)
-        h_augT = _h_aug_t(lib, h, has_bias)
-        dw_augT = torch.zeros(h_augT.shape[0], V, dtype=torch.float32,
-                              device=h.device)
-        for s in range(0, N, C):
-            e = min(N, s + C)
-            if logits_full is not None:
-                dlog = logits_full[s:e]
-            else:
-                dlog = scratch[: e - s]
-                torch.mm(h[s:e], w_t, out=dlog)  # recompute fallback
-            # in-place: dlog <- (softmax(dlog + bias) - onehot) * scale
-            lib.ce_dlogits(dlog, targets[s:e], bias_arg, lse[s:e], scale)
-            torch.mm(dlog, weight, out=dh[s:e])
-            dw_augT += torch.mm(h_augT[:, s:e], dlog)
-        dw, db = _split_dw_aug_t(lib, dw_augT, H, has_bias)
-        return (dh, dw.to(weight.dtype),
-                db.to(ctx.bias_dtype) if has_bias else None, None)
+        return _ce_backward(ctx, dloss)
 
 
 @torch.no_grad()

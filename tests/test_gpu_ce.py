@@ -8,6 +8,8 @@ logit, a relative 2e-4 on p plus one rounding of the storage format (fp32,
 bf16, e4m3) on the dlogits. tied_decoder_ce is held to K * E + floor per
 output, E = max|ce_model - ce_exact| from the CPU, K = 2 (ce_ref.e2e_case).
 quantize_e4m3 must match the fp32 division byte for byte.
+The three two-kernel-path wrappers must refuse a short bias, a short or
+host-side lse and a narrow fp8 output before anything is launched.
 tests/test_ce_ref.py shows each bound is at least 2x below what a dropped
 tail, a misplaced onehot, a wrongly folded bias or a missing scale causes.
 
@@ -46,7 +48,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 BF16, F32 = torch.bfloat16, torch.float32
 
-_ENV = ("CI_CE_FP8R", "CI_CE_CHUNK", "CI_CE_SAVE_LOGITS", "CI_CE_2STREAM")
+_ENV = ("CI_CE_FP8R", "CI_CE_CHUNK", "CI_CE_SAVE_LOGITS")
 
 
 @pytest.fixture(autouse=True)
@@ -205,3 +207,42 @@ def test_quantize_e4m3_matches_division_byte_for_byte(dt, n):
     assert bad.numel() == 0, \
         (bad[:8].tolist(), x[bad[:8]].tolist(), q[bad[:8]].tolist(),
          want[bad[:8]].tolist())
+
+
+# ---- 4. the wrappers' shared argument check --------------------------------
+
+def _refusal_cases():
+    out = [(k, bad) for k in ("ce_rowstats", "ce_dlogits", "ce_dlogits_dual")
+           for bad in ("short_bias", "short_lse", "cpu_lse")]
+    return out + [("ce_dlogits_dual", "narrow_fp8")]
+
+
+@pytest.mark.parametrize("kernel,bad", _refusal_cases())
+@pytest.mark.parametrize("dt", [BF16, F32], ids=["bf16", "fp32"])
+def test_epilogue_wrappers_refuse_bad_arguments(dt, kernel, bad):
+    """A bias of V - 1 elements, an lse of 2 elements for 3 rows, an lse on
+    the CPU and an fp8 output 8 columns short would each hand the kernel an
+    out-of-bounds or host pointer: the wrapper raises before any launch, so
+    the logits keep their bits."""
+    lib = _lib()
+    R, V = 3, 40
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(R, V, generator=g).to(dt).to(DEV)
+    before = x.clone()
+    t = torch.zeros(R, dtype=torch.int64, device=DEV)
+    bias = torch.zeros(V - 1 if bad == "short_bias" else V, dtype=F32,
+                       device=DEV)
+    lse = torch.zeros(2 if bad == "short_lse" else R, dtype=F32,
+                      device="cpu" if bad == "cpu_lse" else DEV)
+    tl = torch.zeros(R, dtype=F32, device=DEV)
+    scale = torch.ones(1, dtype=F32, device=DEV)
+    q8 = torch.zeros(R, V - 8 if bad == "narrow_fp8" else V,
+                     dtype=torch.uint8, device=DEV)
+    args = {"ce_rowstats": (x, t, bias, lse, tl),
+            "ce_dlogits": (x, t, bias, lse, scale),
+            "ce_dlogits_dual": (x, t, bias, lse, scale, q8, C.STORE)}[kernel]
+    with pytest.raises(RuntimeError):
+        getattr(lib, kernel)(*args)
+    torch.cuda.synchronize()
+    bits = torch.int16 if dt == BF16 else torch.int32
+    assert torch.equal(x.view(bits), before.view(bits))
