@@ -17,14 +17,15 @@ import logging
 import os
 import threading
 from pathlib import Path
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Union
 
 import numpy as np
 import torch
 
-from ..models.awd_lstm import AWDLSTM, AWDLSTMEncoder
+from ..models.awd_lstm import AWDLSTM, AWDLSTMEncoder, LinearDecoder
 from ..ops.pool import concat_pool
-from ..text.tokenizer import Tokenizer, Vocab, process_dict as _process_dict
+from ..text.tokenizer import (BOS, UNK, Tokenizer, Vocab, decode_spec_tokens,
+                              process_dict as _process_dict)
 
 log = logging.getLogger(__name__)
 
@@ -38,7 +39,8 @@ class InferenceWrapper:
                  vocab: Optional[Vocab] = None,
                  device: Optional[str] = None,
                  dtype: Optional[torch.dtype] = None,
-                 use_graphs: bool = False):
+                 use_graphs: bool = False,
+                 decoder: Optional[LinearDecoder] = None):
         self.device = torch.device(device) if device else (
             torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu"))
         self.dtype = dtype or (torch.bfloat16 if self.device.type == "cuda"
@@ -47,20 +49,38 @@ class InferenceWrapper:
         if encoder is not None:
             assert vocab is not None
             self.encoder, self.vocab = encoder, vocab
+            self.decoder = decoder
         else:
             root = Path(model_path)
             if model_file_name:
                 root = root / model_file_name
             cfg = json.loads((root / "config.json").read_text())
             self.vocab = Vocab.load(root / "vocab.json")
+            dec_sd = None
+            if cfg.get("decoder_file"):
+                dec_sd = torch.load(root / cfg["decoder_file"],
+                                    map_location="cpu", weights_only=True)
             model = AWDLSTM(vocab_sz=len(self.vocab), emb_sz=cfg["emb_sz"],
                             n_hid=cfg["n_hid"], n_layers=cfg["n_layers"],
-                            qrnn=cfg.get("qrnn", False))
+                            qrnn=cfg.get("qrnn", False),
+                            tie_weights=cfg.get("tie_weights", True),
+                            out_bias=dec_sd is None or "bias" in dec_sd)
             enc_file = root / cfg.get("encoder_file", "encoder.pth")
             model.load_encoder(enc_file)
             self.encoder = model.encoder
+            self.decoder = decoder
+            if dec_sd is not None and decoder is None:
+                # strict=False: a tied weight lives in encoder.pth only
+                model.decoder.decoder.load_state_dict(dec_sd, strict=False)
+                self.decoder = model.decoder
         self.encoder = self.encoder.to(device=self.device, dtype=self.dtype)
         self.encoder.eval()
+        self._lm: Optional[AWDLSTM] = None
+        if self.decoder is not None:
+            # moving the encoder first keeps a tied weight one Parameter
+            self.decoder = self.decoder.to(device=self.device, dtype=self.dtype)
+            self.decoder.eval()
+            self._lm = AWDLSTM.from_parts(self.encoder, self.decoder)
         self.emb_sz = self.encoder.emb_sz
         self.pad_idx = self.encoder.pad_token
         self._graphs = {}
@@ -138,6 +158,34 @@ class InferenceWrapper:
         lens = torch.tensor([len(ids)], device=self.device)
         return self._encode_batch(t, lens).cpu()
 
+    def predict(self, text: str, n_words: int = 1, no_unk: bool = True,
+                temperature: float = 1.0, min_p: Optional[float] = None,
+                sep: str = " ", seed: Optional[int] = None,
+                n_samples: int = 1) -> Union[str, List[str]]:
+        """Continue ``text`` by ``n_words`` sampled tokens — fastai
+        ``LanguageLearner.predict`` (the reference's post-pretraining check,
+        04_Inference.ipynb). Returns ``text + sep + continuation``; with
+        ``n_samples > 1`` a list of that many continuations of the same
+        prompt, each drawn with its own stream of uniforms."""
+        if self._lm is None:
+            raise RuntimeError(
+                "this artifact has no decoder, so it cannot generate text: "
+                "export it with save_artifacts(..., with_decoder=True)")
+        if n_samples < 1:
+            raise ValueError(f"n_samples must be >= 1 (got {n_samples})")
+        stoi = self.vocab.stoi
+        unk = stoi.get(UNK, 0)
+        ids = self.numericalize(text) or [stoi.get(BOS, unk)]
+        prompt = torch.tensor([ids] * n_samples, dtype=torch.int64,
+                              device=self.device)
+        with self._encode_lock:
+            out, _ = self._lm.generate(prompt, n_words, temperature=temperature,
+                                       min_p=min_p, no_unk=no_unk, unk_idx=unk,
+                                       seed=seed)
+        texts = [text + sep + sep.join(decode_spec_tokens(
+            self.vocab.itos[i] for i in row)) for row in out.cpu().tolist()]
+        return texts[0] if n_samples == 1 else texts
+
     def df_to_embedding(self, dataframe, bs: int = 100) -> np.ndarray:
         """Bulk path (inference.py:138-229): build docs from (title, body)
         rows, sort by length, pad per batch, encode, unsort. OOM -> bs//2."""
@@ -192,14 +240,25 @@ class InferenceWrapper:
         return concat_pool(hidden, lengths)
 
 
-def save_artifacts(model: AWDLSTM, vocab: Vocab, path) -> None:
-    """Write the artifact layout InferenceWrapper loads."""
+def save_artifacts(model: AWDLSTM, vocab: Vocab, path,
+                   with_decoder: bool = False) -> None:
+    """Write the artifact layout InferenceWrapper loads. ``with_decoder``
+    adds ``decoder.pth`` (the output bias, and the weight when it is not tied
+    to the embedding) so the served model can ``predict`` text."""
     root = Path(path)
     root.mkdir(parents=True, exist_ok=True)
     enc = model.encoder
-    (root / "config.json").write_text(json.dumps({
+    cfg = {
         "emb_sz": enc.emb_sz, "n_hid": enc.n_hid, "n_layers": enc.n_layers,
         "qrnn": bool(getattr(enc, "qrnn", False)),
-        "encoder_file": "encoder.pth"}))
+        "encoder_file": "encoder.pth"}
+    if with_decoder:
+        lin = model.decoder.decoder
+        tied = lin.weight is enc.encoder.weight
+        cfg["decoder_file"] = "decoder.pth"
+        cfg["tie_weights"] = tied
+        torch.save({k: v for k, v in lin.state_dict().items()
+                    if not (tied and k == "weight")}, root / "decoder.pth")
+    (root / "config.json").write_text(json.dumps(cfg))
     vocab.save(root / "vocab.json")
     model.save_encoder(root / "encoder.pth")

@@ -364,6 +364,15 @@ class AWDLSTM(nn.Module):
                                 bias=out_bias)
         self.layers = nn.ModuleList([encoder, decoder])
 
+    @classmethod
+    def from_parts(cls, encoder: AWDLSTMEncoder,
+                   decoder: LinearDecoder) -> "AWDLSTM":
+        """Wrap an existing encoder and decoder (shared, not copied)."""
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        self.layers = nn.ModuleList([encoder, decoder])
+        return self
+
     def __getitem__(self, idx: int) -> nn.Module:
         return self.layers[idx]
 
@@ -380,6 +389,71 @@ class AWDLSTM(nn.Module):
 
     def forward(self, input_ids: Tensor):
         return self.layers[1](self.layers[0](input_ids))
+
+    # --- text generation (fastai LanguageLearner.predict) -------------------
+    def generate(self, prompt_ids: Tensor, n_words: int,
+                 temperature: float = 1.0, min_p: Optional[float] = None,
+                 no_unk: bool = True, unk_idx: int = 0,
+                 seed: Optional[int] = None,
+                 uniforms: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        """Sample ``n_words`` continuation ids for every row of ``prompt_ids``
+        ((B,T), equal lengths, no padding). Returns ``(ids (B, n_words) int64,
+        logp (B, n_words) fp32)``; ``logp`` is each chosen id's temperature-1
+        log-probability.
+
+        The model is reset, reads the prompt once, and then feeds every
+        sampled id back as a one-token input; the hidden state carries. Each
+        word is one ``ops.sample_next`` (K10) into column ``step`` of the
+        outputs, so on a GPU the ids never visit the host inside the loop.
+        ``uniforms`` (n_words, B) in [0,1) replaces the draw of
+        ``torch.rand`` from a generator seeded with ``seed``. Runs in eval
+        mode under ``no_grad``; training flags are restored afterwards."""
+        if prompt_ids.dim() != 2 or prompt_ids.size(1) < 1:
+            raise ValueError("prompt_ids must be (B, T) with T >= 1")
+        if n_words < 0:
+            raise ValueError(f"n_words must be >= 0 (got {n_words})")
+        from ..ops.decode import sample_next, _n_tiles
+        B = prompt_ids.size(0)
+        lin = self.decoder.decoder
+        dev = lin.weight.device
+        V = lin.weight.size(0)
+        if uniforms is None:
+            gen = torch.Generator(device=dev)
+            if seed is None:
+                gen.seed()
+            else:
+                gen.manual_seed(int(seed))
+            uniforms = torch.rand(n_words, B, device=dev, generator=gen)
+        elif tuple(uniforms.shape) != (n_words, B):
+            raise ValueError(f"uniforms must be ({n_words}, {B}), got "
+                             f"{tuple(uniforms.shape)}")
+        uniforms = uniforms.to(device=dev)
+        ids = torch.zeros(B, n_words, dtype=torch.int64, device=dev)
+        logp = torch.zeros(B, n_words, dtype=torch.float32, device=dev)
+        scratch = None
+        if dev.type == "cuda":
+            scratch = (torch.empty(B, V, device=dev, dtype=torch.float32),
+                       torch.empty(B, _n_tiles(V), 2, device=dev,
+                                   dtype=torch.float32))
+        flags = [(m, m.training) for m in self.modules()]
+        for m, _ in flags:
+            m.training = False
+        try:
+            with torch.no_grad():
+                self.reset(B)
+                x = prompt_ids.to(dev)
+                for step in range(n_words):
+                    _, outputs = self.encoder(x)
+                    sample_next(outputs[-1][:, -1], lin.weight, lin.bias,
+                                uniforms[step], temperature, min_p,
+                                unk_idx if no_unk else -1,
+                                out_ids=ids[:, step], out_logp=logp[:, step],
+                                scratch=scratch)
+                    x = ids[:, step:step + 1]
+        finally:
+            for m, f in flags:
+                m.training = f
+        return ids, logp
 
     # --- fastai-compatible (de)serialization -------------------------------
     def save_encoder(self, path) -> None:

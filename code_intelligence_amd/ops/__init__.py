@@ -1,15 +1,17 @@
 """HIP/CDNA4 op layer: dispatch between gfx950 kernels (ROCm) and the
 pure-PyTorch CPU reference implementations. See SURVEY.md §2.4 for the
-kernel inventory (K1-K9)."""
+kernel inventory (K1-K9); K10 (decode-and-sample) is in ARCHITECTURE.md."""
 from . import extension
 from .lstm import lstm_forward
 from .pool import concat_pool, StreamingConcatPool, pool_head
 from .dropout import variational_dropout
 from .crossentropy import tied_decoder_ce, TiedDecoderCE
 from .adam import FusedAdamW
+from .decode import decode_logits, sample_next
 
 __all__ = [
     "extension", "lstm_forward", "concat_pool", "StreamingConcatPool",
     "pool_head", "variational_dropout",
     "tied_decoder_ce", "TiedDecoderCE", "FusedAdamW",
+    "decode_logits", "sample_next",
 ]

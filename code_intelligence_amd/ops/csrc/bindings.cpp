@@ -75,6 +75,12 @@ void pack_kmajor(at::Tensor src, at::Tensor dst, long row_off, long col_off);
 std::tuple<at::Tensor, at::Tensor> lstm_weight_grads(
     at::Tensor dgates, at::Tensor x_tm, at::Tensor hs, at::Tensor h0,
     bool need_ih, bool need_hh);
+void decode_logits(at::Tensor h, at::Tensor weight,
+                   c10::optional<at::Tensor> bias, at::Tensor logits,
+                   at::Tensor partials);
+void decode_sample(at::Tensor logits, at::Tensor partials, at::Tensor u,
+                   double temperature, double min_p, long unk,
+                   at::Tensor out_ids, at::Tensor out_logp);
 }  // namespace ci
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -145,4 +151,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "LSTM dW_ih/dW_hh: K-major pack of [x ; h_prev] + one NN GEMM",
         py::arg("dgates"), py::arg("x_tm"), py::arg("hs"), py::arg("h0"),
         py::arg("need_ih") = true, py::arg("need_hh") = true);
+  m.def("decode_logits", &ci::decode_logits,
+        "decoder GEMV for <= 8 rows per read of W -> fp32 logits + per-tile "
+        "(max, sum exp) partials",
+        py::arg("h"), py::arg("weight"), py::arg("bias"), py::arg("logits"),
+        py::arg("partials"));
+  m.def("decode_sample", &ci::decode_sample,
+        "no_unk / min_p / temperature inverse-CDF draw from decode_logits' "
+        "output; writes id (int64) and temperature-1 log-prob per row",
+        py::arg("logits"), py::arg("partials"), py::arg("u"),
+        py::arg("temperature"), py::arg("min_p"), py::arg("unk"),
+        py::arg("out_ids"), py::arg("out_logp"));
 }

@@ -33,6 +33,7 @@ SOURCES = [
     "lstm_gemv.hip",
     "pool.hip",
     "pool_stream.hip",
+    "decode.hip",
     "qrnn_pool.hip",
     "adam.hip",
     "ce.hip",

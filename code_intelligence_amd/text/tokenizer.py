@@ -128,6 +128,46 @@ def deal_caps(toks: List[str]) -> List[str]:
 default_post_rules = [replace_all_caps, deal_caps]
 
 
+def decode_spec_tokens(tokens: Iterable[str]) -> List[str]:
+    """Undo the caps and repetition markers in generated tokens (fastai's
+    default ``decoder`` of ``LanguageLearner.predict``): ``xxmaj w`` -> ``W``,
+    ``xxup w`` -> ``W`` upper-cased, ``xxrep n c`` -> ``c`` * n,
+    ``xxwrep n w`` -> ``w`` n times. A marker at the end of the sequence, or a
+    repetition whose count is not a number, is passed through unchanged."""
+    out: List[str] = []
+    rule: Optional[str] = None
+    count: Optional[int] = None
+    for t in tokens:
+        if rule is None:
+            if t in (TK_MAJ, TK_UP, TK_REP, TK_WREP):
+                rule = t
+            else:
+                out.append(t)
+        elif rule == TK_MAJ:
+            out.append(t[:1].upper() + t[1:].lower())
+            rule = None
+        elif rule == TK_UP:
+            out.append(t.upper())
+            rule = None
+        elif count is None:
+            try:
+                count = int(t)
+            except ValueError:
+                out += [rule, t]
+                rule = None
+        else:
+            if rule == TK_REP:
+                out.append(t * count)
+            else:
+                out += [t] * count
+            rule, count = None, None
+    if rule is not None:
+        out.append(rule)
+        if count is not None:
+            out.append(str(count))
+    return out
+
+
 class Tokenizer:
     """pre_rules (str->str) -> regex word split -> post_rules (tokens->tokens).
 
