@@ -28,7 +28,27 @@ void fused_adamw(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
                  std::vector<at::Tensor> eass, double lr, double b1, double b2,
                  double eps, double wd, double bc1, double bc2) {
   const int threads = 256;
-  for (size_t k = 0; k < params.size(); ++k) {
+  const size_t np = params.size();
+  TORCH_CHECK(grads.size() == np && masters.size() == np &&
+              eas_.size() == np && eass.size() == np,
+              "fused_adamw: one grad, master and moment pair per parameter");
+  // check every tensor before the first launch: a refusal updates nothing
+  for (size_t k = 0; k < np; ++k) {
+    auto& p = params[k];
+    CI_CHECK_CUDA(p); CI_CHECK_CONTIG(p);
+    CI_CHECK_CUDA(grads[k]); CI_CHECK_CONTIG(grads[k]);
+    TORCH_CHECK(grads[k].scalar_type() == p.scalar_type() &&
+                grads[k].numel() == p.numel(),
+                "fused_adamw: grad must have its parameter's dtype and numel");
+    for (const at::Tensor* s : {&masters[k], &eas_[k], &eass[k]}) {
+      CI_CHECK_CUDA(*s); CI_CHECK_CONTIG(*s);
+      TORCH_CHECK(s->scalar_type() == at::ScalarType::Float &&
+                  s->numel() == p.numel(),
+                  "fused_adamw: master and moments must be fp32 with the "
+                  "parameter's numel");
+    }
+  }
+  for (size_t k = 0; k < np; ++k) {
     auto& p = params[k];
     const long n = p.numel();
     const bool has_master = masters[k].data_ptr() != p.data_ptr();

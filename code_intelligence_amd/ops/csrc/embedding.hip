@@ -39,8 +39,23 @@ __global__ void emb_scatter_kernel(const T* __restrict__ gout,
   atomicAdd(dweight + row * E + e, v);
 }
 
+// ids are read as int64 and rowmask as fp32 device pointers, rowmask[row]
+// for every row looked up: refuse anything else before the launch
+static void check_ids_rowmask(const at::Tensor& ids, const at::Tensor& rowmask,
+                              long V) {
+  CI_CHECK_CUDA(ids);
+  TORCH_CHECK(ids.scalar_type() == at::ScalarType::Long, "ids must be int64");
+  CI_CHECK_CUDA(rowmask); CI_CHECK_CONTIG(rowmask);
+  TORCH_CHECK(rowmask.scalar_type() == at::ScalarType::Float,
+              "rowmask must be fp32");
+  TORCH_CHECK(rowmask.numel() == 0 || rowmask.numel() == V,
+              "rowmask must be empty or hold one value per table row");
+}
+
 at::Tensor emb_gather(at::Tensor weight, at::Tensor ids, at::Tensor rowmask) {
   CI_CHECK_CUDA(weight); CI_CHECK_CONTIG(weight); CI_CHECK_CONTIG(ids);
+  TORCH_CHECK(weight.dim() == 2, "weight must be (V,E)");
+  check_ids_rowmask(ids, rowmask, weight.size(0));
   const int E = weight.size(1);
   const long n_tok = ids.numel();
   auto sizes = ids.sizes().vec();
@@ -61,9 +76,11 @@ at::Tensor emb_gather(at::Tensor weight, at::Tensor ids, at::Tensor rowmask) {
 at::Tensor emb_scatter(at::Tensor gout, at::Tensor ids, at::Tensor rowmask,
                        long V, long pad_idx) {
   CI_CHECK_CUDA(gout); CI_CHECK_CONTIG(ids);
+  check_ids_rowmask(ids, rowmask, V);
   auto gc = gout.contiguous();
   const int E = gc.size(-1);
   const long n_tok = ids.numel();
+  TORCH_CHECK(gc.numel() == n_tok * E, "gout must be ids' shape + (E)");
   auto dw = at::zeros({V, (long)E}, gc.options().dtype(at::ScalarType::Float));
   const int threads = 256;
   CI_DISPATCH_FB(gc.scalar_type(), "emb_scatter", [&] {

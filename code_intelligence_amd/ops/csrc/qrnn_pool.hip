@@ -167,6 +167,8 @@ __global__ void qrnn_fo_bwd_kernel_vec(const T* __restrict__ gates,
 
 std::vector<at::Tensor> qrnn_fo_pool_fwd(at::Tensor gates, at::Tensor c0) {
   CI_CHECK_CUDA(gates); CI_CHECK_CONTIG(gates); CI_CHECK_CONTIG(c0);
+  CI_CHECK_CUDA(c0);
+  TORCH_CHECK(gates.dim() == 3 && c0.dim() == 2, "gates (B,T,3H), c0 (B,H)");
   const int B = gates.size(0), Tn = gates.size(1), H3 = gates.size(2);
   TORCH_CHECK(H3 % 3 == 0, "gates last dim must be 3*H");
   const int H = H3 / 3;
@@ -203,7 +205,25 @@ std::vector<at::Tensor> qrnn_fo_pool_bwd(at::Tensor gates, at::Tensor c,
                                          at::Tensor dcT) {
   CI_CHECK_CUDA(gates); CI_CHECK_CONTIG(gates); CI_CHECK_CONTIG(c);
   CI_CHECK_CONTIG(c0); CI_CHECK_CONTIG(dh); CI_CHECK_CONTIG(dcT);
+  TORCH_CHECK(gates.dim() == 3 && gates.size(2) % 3 == 0,
+              "gates must be (B,T,3H)");
   const int B = gates.size(0), Tn = gates.size(1), H = gates.size(2) / 3;
+  // every pointer below is reinterpreted as gates' dtype and indexed by
+  // gates' shape: refuse anything else before the launch
+  for (const at::Tensor* t : {&c, &dh}) {
+    CI_CHECK_CUDA(*t);
+    TORCH_CHECK(t->scalar_type() == gates.scalar_type(),
+                "qrnn_fo_pool_bwd: c and dh must have gates' dtype");
+    TORCH_CHECK(t->dim() == 3 && t->size(0) == B && t->size(1) == Tn &&
+                t->size(2) == H, "qrnn_fo_pool_bwd: c and dh must be (B,T,H)");
+  }
+  for (const at::Tensor* t : {&c0, &dcT}) {
+    CI_CHECK_CUDA(*t);
+    TORCH_CHECK(t->scalar_type() == gates.scalar_type(),
+                "qrnn_fo_pool_bwd: c0 and dcT must have gates' dtype");
+    TORCH_CHECK(t->dim() == 2 && t->size(0) == B && t->size(1) == H,
+                "qrnn_fo_pool_bwd: c0 and dcT must be (B,H)");
+  }
   auto dgates = at::empty_like(gates);
   auto dc0 = at::empty_like(c0);
   const int threads = 256;

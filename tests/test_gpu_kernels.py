@@ -492,10 +492,12 @@ def test_artar_fused_matches_eager(dtype):
     (ref * 1.7).backward()
     tol = 1e-4 if dtype == torch.float32 else 0.02
     assert abs(float(reg) - float(ref)) / float(ref) < tol
-    assert torch.allclose(out.grad.float(), out2.grad, atol=tol), \
-        (out.grad.float() - out2.grad).abs().max()
-    assert torch.allclose(r.grad.float(), r2.grad, atol=tol), \
-        (r.grad.float() - r2.grad).abs().max()
+    # relative to the largest gradient (2e-3 to 6e-3 here): one bf16
+    # rounding, or 1e-5 in fp32
+    tol_rel = 1e-5 if dtype == torch.float32 else 2.0 ** -8
+    for got, want in ((out.grad, out2.grad), (r.grad, r2.grad)):
+        err = (got.float() - want).abs().max()
+        assert err <= tol_rel * want.abs().max(), (err, want.abs().max())
 
 
 def test_artar_loss_trainer_path_gpu():
@@ -563,8 +565,9 @@ def test_artar_engages_on_trainer_layout():
         1.0 * (r2[:, 1:] - r2[:, :-1]).pow(2).mean()
     ref.backward()
     assert abs(float(reg) - float(ref)) / float(ref) < 0.02
-    assert torch.allclose(out.grad.float(), out2.grad, atol=0.02)
-    assert torch.allclose(r.grad.float(), r2.grad, atol=0.02)
+    for got, want in ((out.grad, out2.grad), (r.grad, r2.grad)):
+        err = (got.float() - want).abs().max()
+        assert err <= 2.0 ** -8 * want.abs().max(), (err, want.abs().max())
 
 
 # ---- fp8 LSTM GEMM path (CI_LSTM_FP8, round 2) ----------------------------
