@@ -186,6 +186,32 @@ class InferenceWrapper:
             self.vocab.itos[i] for i in row)) for row in out.cpu().tolist()]
         return texts[0] if n_samples == 1 else texts
 
+    def beam_search(self, text: str, n_words: int, no_unk: bool = True,
+                    top_k: int = 10, beam_sz: int = 1000,
+                    temperature: float = 1.0, sep: str = " ",
+                    decoder=decode_spec_tokens,
+                    seed: Optional[int] = None) -> str:
+        """Continue ``text`` by ``n_words`` tokens found by beam search —
+        fastai ``LanguageLearner.beam_search``: every word keeps the
+        ``beam_sz`` best of each beam's ``top_k`` continuations, and one of
+        the final beams is drawn with probability proportional to
+        ``exp(-score / temperature)``. Returns ``text + sep + continuation``;
+        deterministic for a given ``seed``."""
+        if self._lm is None:
+            raise RuntimeError(
+                "this artifact has no decoder, so it cannot generate text: "
+                "export it with save_artifacts(..., with_decoder=True)")
+        stoi = self.vocab.stoi
+        unk = stoi.get(UNK, 0)
+        ids = self.numericalize(text) or [stoi.get(BOS, unk)]
+        prompt = torch.tensor([ids], dtype=torch.int64, device=self.device)
+        with self._encode_lock:
+            out, _, _ = self._lm.beam_search(
+                prompt, n_words, top_k=top_k, beam_sz=beam_sz, no_unk=no_unk,
+                unk_idx=unk, temperature=temperature, seed=seed)
+        return text + sep + sep.join(decoder(
+            self.vocab.itos[i] for i in out.tolist()))
+
     def df_to_embedding(self, dataframe, bs: int = 100) -> np.ndarray:
         """Bulk path (inference.py:138-229): build docs from (title, body)
         rows, sort by length, pad per batch, encode, unsort. OOM -> bs//2."""

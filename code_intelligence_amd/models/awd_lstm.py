@@ -40,6 +40,13 @@ __all__ = [
     "awd_lstm_lm_config",
 ]
 
+# beam_search on a GPU: up to this many beam rows the logits come from
+# ops.decode_logits (one read of the decoder weight per 8 rows), above it from
+# one library GEMM. Measured with scripts/beam_bench.py --sweep at the deployed
+# shape: the two tie at 1 row and the GEMM wins by more than the spread from 2
+# rows on (profiles/BENCH_HISTORY.md, NOTES.md "Beam search").
+BEAM_GEMM_CROSSOVER = 1
+
 # fastai's awd_lstm_lm_config defaults, as mutated by the reference
 # (train.py:68-73): output_p .1, hidden_p .15, input_p .25, embed_p .02,
 # weight_p .2, tie_weights True, out_bias True.
@@ -292,7 +299,20 @@ class AWDLSTMEncoder(nn.Module):
                 rnn.reset()  # QRNN: clear the saved window-2 prev_x
 
     def select_hidden(self, idxs: Tensor) -> None:
+        """Reorder (and resize) the carried state to rows ``idxs``: beam
+        search keeps the state of each surviving beam's parent. Covers
+        ``(h, c)`` and a QRNN layer's saved window-2 ``prev_x``."""
         self.hidden = [(h[idxs], c[idxs]) for h, c in self.hidden]
+        for rnn in self.rnns:
+            prev = getattr(rnn, "prev_x", None)
+            if prev is None:
+                continue
+            picked = prev[idxs]
+            if picked.shape == prev.shape:
+                # same stable-buffer rule as WeightDroppedQRNN.forward
+                prev.copy_(picked)
+            else:
+                rnn.prev_x = picked
         self.bs = len(idxs)
 
     def forward(self, input_ids: Tensor, from_embeddings: bool = False
@@ -454,6 +474,119 @@ class AWDLSTM(nn.Module):
             for m, f in flags:
                 m.training = f
         return ids, logp
+
+    # --- beam search (fastai LanguageLearner.beam_search) -------------------
+    def beam_search(self, prompt_ids: Tensor, n_words: int, top_k: int = 10,
+                    beam_sz: int = 1000, no_unk: bool = True, unk_idx: int = 0,
+                    temperature: float = 1.0, seed: Optional[int] = None,
+                    uniform: Optional[float] = None
+                    ) -> Tuple[Tensor, Tensor, Tensor]:
+        """Beam-search ``n_words`` continuation ids for one prompt
+        (``prompt_ids`` (1,T)). Returns ``(ids (n_words,) int64, nodes
+        (B_final, n_words) int64, scores (B_final,))``, all on the host:
+        ``nodes`` are the surviving beams in ascending score order, ``scores``
+        their summed negative log-probabilities (fp32; the model's dtype on
+        the CPU path of an fp32 / fp64 model), ``ids`` the beam drawn at the
+        end.
+
+        Each word: one-token encoder step for every beam, logits
+        (``ops.decode_logits`` up to ``BEAM_GEMM_CROSSOVER`` rows, one library
+        GEMM above), ``ops.topk_logprobs`` and ``ops.beam_select`` (K11) into
+        row ``step`` of preallocated ``(n_words, beam_sz)`` token / parent /
+        score buffers, ``select_hidden(parent)``; the next input is a view of
+        the token row. Nothing is read on the host inside the loop. Afterwards
+        the buffers are copied once, the parents are back-tracked into
+        ``nodes``, and one beam is chosen with probability proportional to
+        ``exp(-score / temperature)`` by an fp64 inverse-CDF draw against
+        ``uniform`` (default: one ``torch.rand`` from a generator seeded with
+        ``seed``): the first beam whose running sum exceeds ``uniform * total``,
+        the last one if none does. Runs in eval mode under ``no_grad``;
+        training flags are restored afterwards."""
+        if prompt_ids.dim() != 2 or prompt_ids.size(0) != 1 \
+                or prompt_ids.size(1) < 1:
+            raise ValueError("prompt_ids must be (1, T) with T >= 1")
+        if n_words < 0:
+            raise ValueError(f"n_words must be >= 0 (got {n_words})")
+        if beam_sz < 1:
+            raise ValueError(f"beam_sz must be >= 1 (got {beam_sz})")
+        if not temperature > 0:
+            raise ValueError(f"temperature must be > 0 (got {temperature})")
+        if uniform is not None and not 0.0 <= uniform < 1.0:
+            raise ValueError(f"uniform must be in [0, 1) (got {uniform})")
+        from ..ops.beam import (MAX_CANDIDATES, MAX_K, beam_select,
+                                topk_logprobs)
+        from ..ops.decode import decode_logits
+        lin = self.decoder.decoder
+        dev = lin.weight.device
+        V = lin.weight.size(0)
+        unk = unk_idx if no_unk else -1
+        if not -1 <= unk < V:
+            raise ValueError(f"unk_idx must be in [-1, {V}) (got {unk_idx})")
+        if not 1 <= top_k <= MAX_K:
+            raise ValueError(f"top_k must be in [1, {MAX_K}] (got {top_k})")
+        if top_k > V - (unk >= 0):
+            raise ValueError(f"top_k={top_k} exceeds the {V - (unk >= 0)} "
+                             "candidates of a row")
+        # rows per word: 1, then min(beam_sz, rows * top_k)
+        rows = [1]
+        for _ in range(n_words):
+            rows.append(min(beam_sz, rows[-1] * top_k))
+        if n_words and max(rows[:-1]) * top_k > MAX_CANDIDATES:
+            raise ValueError(
+                f"{max(rows[:-1])} beams x top_k={top_k} candidates exceed "
+                f"{MAX_CANDIDATES}: lower beam_sz or top_k")
+        width = max(rows)
+        on_gpu = dev.type == "cuda"
+        sdtype = torch.float32 if on_gpu or lin.weight.dtype not in (
+            torch.float32, torch.float64) else lin.weight.dtype
+        token = torch.zeros(n_words, width, dtype=torch.int64, device=dev)
+        parent = torch.zeros(n_words, width, dtype=torch.int64, device=dev)
+        score = torch.zeros(n_words + 1, width, dtype=sdtype, device=dev)
+        flags = [(m, m.training) for m in self.modules()]
+        for m, _ in flags:
+            m.training = False
+        try:
+            with torch.no_grad():
+                self.reset(1)
+                x = prompt_ids.to(dev)
+                for step in range(n_words):
+                    B, Bn = rows[step], rows[step + 1]
+                    _, outputs = self.encoder(x)
+                    h = outputs[-1][:, -1]
+                    if on_gpu and B <= BEAM_GEMM_CROSSOVER:
+                        logits, _ = decode_logits(h, lin.weight, lin.bias)
+                    else:
+                        logits = nn.functional.linear(h, lin.weight, lin.bias)
+                    vals, idx = topk_logprobs(logits, top_k, unk)
+                    beam_select(score[step, :B], vals.to(sdtype), idx, beam_sz,
+                                out=(score[step + 1, :Bn], parent[step, :Bn],
+                                     token[step, :Bn]))
+                    self.encoder.select_hidden(parent[step, :Bn])
+                    x = token[step, :Bn].unsqueeze(1)
+        finally:
+            for m, f in flags:
+                m.training = f
+        # the one copy to the host
+        B = rows[-1]
+        token, parent = token.cpu(), parent.cpu()
+        scores = score[n_words, :B].cpu()
+        nodes = torch.zeros(B, n_words, dtype=torch.int64)
+        at = torch.arange(B)
+        for step in range(n_words - 1, -1, -1):
+            nodes[:, step] = token[step][at]
+            at = parent[step][at]
+        s = scores.double() / float(temperature)
+        cdf = torch.exp(s.min() - s).cumsum(0)
+        if uniform is None:
+            gen = torch.Generator()
+            if seed is None:
+                gen.seed()
+            else:
+                gen.manual_seed(int(seed))
+            uniform = float(torch.rand(1, generator=gen, dtype=torch.float64))
+        target = torch.tensor([uniform * float(cdf[-1])], dtype=torch.float64)
+        pick = min(int(torch.searchsorted(cdf, target, right=True)), B - 1)
+        return nodes[pick].clone(), nodes, scores
 
     # --- fastai-compatible (de)serialization -------------------------------
     def save_encoder(self, path) -> None:

@@ -81,6 +81,11 @@ void decode_logits(at::Tensor h, at::Tensor weight,
 void decode_sample(at::Tensor logits, at::Tensor partials, at::Tensor u,
                    double temperature, double min_p, long unk,
                    at::Tensor out_ids, at::Tensor out_logp);
+void topk_logprobs(at::Tensor logits, long k, long unk, at::Tensor out_vals,
+                   at::Tensor out_idx);
+void beam_select(at::Tensor scores, at::Tensor vals, at::Tensor idx,
+                 long beam_sz, at::Tensor out_scores, at::Tensor out_parent,
+                 at::Tensor out_token);
 }  // namespace ci
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -162,4 +167,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("logits"), py::arg("partials"), py::arg("u"),
         py::arg("temperature"), py::arg("min_p"), py::arg("unk"),
         py::arg("out_ids"), py::arg("out_logp"));
+  m.def("topk_logprobs", &ci::topk_logprobs,
+        "k largest log-probabilities of every row of logits, descending, "
+        "ties to the lower index; unk is never returned",
+        py::arg("logits"), py::arg("k"), py::arg("unk"), py::arg("out_vals"),
+        py::arg("out_idx"));
+  m.def("beam_select", &ci::beam_select,
+        "best min(beam_sz, B*k) of the candidates score[b] - vals[b][j], "
+        "ascending, ties to the lower flat index; writes score, parent row "
+        "and token",
+        py::arg("scores"), py::arg("vals"), py::arg("idx"),
+        py::arg("beam_sz"), py::arg("out_scores"), py::arg("out_parent"),
+        py::arg("out_token"));
 }

@@ -34,6 +34,7 @@ SOURCES = [
     "pool.hip",
     "pool_stream.hip",
     "decode.hip",
+    "beam.hip",
     "qrnn_pool.hip",
     "adam.hip",
     "ce.hip",
