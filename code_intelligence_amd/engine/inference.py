@@ -161,12 +161,16 @@ class InferenceWrapper:
     def predict(self, text: str, n_words: int = 1, no_unk: bool = True,
                 temperature: float = 1.0, min_p: Optional[float] = None,
                 sep: str = " ", seed: Optional[int] = None,
-                n_samples: int = 1) -> Union[str, List[str]]:
+                n_samples: int = 1, top_k: Optional[int] = None,
+                top_p: Optional[float] = None) -> Union[str, List[str]]:
         """Continue ``text`` by ``n_words`` sampled tokens — fastai
         ``LanguageLearner.predict`` (the reference's post-pretraining check,
         04_Inference.ipynb). Returns ``text + sep + continuation``; with
         ``n_samples > 1`` a list of that many continuations of the same
-        prompt, each drawn with its own stream of uniforms."""
+        prompt, each drawn with its own stream of uniforms. ``top_k`` /
+        ``top_p`` restrict every draw to the k most likely words / the
+        smallest set of words that holds ``top_p`` of the probability
+        (``AWDLSTM.generate``); ``None`` is no filter."""
         if self._lm is None:
             raise RuntimeError(
                 "this artifact has no decoder, so it cannot generate text: "
@@ -181,7 +185,7 @@ class InferenceWrapper:
         with self._encode_lock:
             out, _ = self._lm.generate(prompt, n_words, temperature=temperature,
                                        min_p=min_p, no_unk=no_unk, unk_idx=unk,
-                                       seed=seed)
+                                       seed=seed, top_k=top_k, top_p=top_p)
         texts = [text + sep + sep.join(decode_spec_tokens(
             self.vocab.itos[i] for i in row)) for row in out.cpu().tolist()]
         return texts[0] if n_samples == 1 else texts

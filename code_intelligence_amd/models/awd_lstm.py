@@ -415,7 +415,9 @@ class AWDLSTM(nn.Module):
                  temperature: float = 1.0, min_p: Optional[float] = None,
                  no_unk: bool = True, unk_idx: int = 0,
                  seed: Optional[int] = None,
-                 uniforms: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+                 uniforms: Optional[Tensor] = None,
+                 top_k: Optional[int] = None,
+                 top_p: Optional[float] = None) -> Tuple[Tensor, Tensor]:
         """Sample ``n_words`` continuation ids for every row of ``prompt_ids``
         ((B,T), equal lengths, no padding). Returns ``(ids (B, n_words) int64,
         logp (B, n_words) fp32)``; ``logp`` is each chosen id's temperature-1
@@ -426,13 +428,17 @@ class AWDLSTM(nn.Module):
         word is one ``ops.sample_next`` (K10) into column ``step`` of the
         outputs, so on a GPU the ids never visit the host inside the loop.
         ``uniforms`` (n_words, B) in [0,1) replaces the draw of
-        ``torch.rand`` from a generator seeded with ``seed``. Runs in eval
+        ``torch.rand`` from a generator seeded with ``seed``. ``top_k`` /
+        ``top_p`` restrict every draw to the top-k / nucleus set
+        (``ops.decode``; one more launch per word, ``ops.decode_cutoff``, into
+        a buffer allocated once); ``None`` is no filter. Runs in eval
         mode under ``no_grad``; training flags are restored afterwards."""
         if prompt_ids.dim() != 2 or prompt_ids.size(1) < 1:
             raise ValueError("prompt_ids must be (B, T) with T >= 1")
         if n_words < 0:
             raise ValueError(f"n_words must be >= 0 (got {n_words})")
-        from ..ops.decode import sample_next, _n_tiles
+        from ..ops.decode import _check_filters, _n_tiles, sample_next
+        k, tp = _check_filters(top_k, top_p)
         B = prompt_ids.size(0)
         lin = self.decoder.decoder
         dev = lin.weight.device
@@ -450,11 +456,13 @@ class AWDLSTM(nn.Module):
         uniforms = uniforms.to(device=dev)
         ids = torch.zeros(B, n_words, dtype=torch.int64, device=dev)
         logp = torch.zeros(B, n_words, dtype=torch.float32, device=dev)
-        scratch = None
+        scratch = cut = None
         if dev.type == "cuda":
             scratch = (torch.empty(B, V, device=dev, dtype=torch.float32),
                        torch.empty(B, _n_tiles(V), 2, device=dev,
                                    dtype=torch.float32))
+            if k > 0 or tp > 0.0:
+                cut = torch.empty(B, device=dev, dtype=torch.float32)
         flags = [(m, m.training) for m in self.modules()]
         for m, _ in flags:
             m.training = False
@@ -468,7 +476,8 @@ class AWDLSTM(nn.Module):
                                 uniforms[step], temperature, min_p,
                                 unk_idx if no_unk else -1,
                                 out_ids=ids[:, step], out_logp=logp[:, step],
-                                scratch=scratch)
+                                scratch=scratch, top_k=top_k, top_p=top_p,
+                                cut_scratch=cut)
                     x = ids[:, step:step + 1]
         finally:
             for m, f in flags:

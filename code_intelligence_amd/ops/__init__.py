@@ -8,12 +8,12 @@ from .pool import concat_pool, StreamingConcatPool, pool_head
 from .dropout import variational_dropout
 from .crossentropy import tied_decoder_ce, TiedDecoderCE
 from .adam import FusedAdamW
-from .decode import decode_logits, sample_next
+from .decode import decode_cutoff, decode_logits, sample_next
 from .beam import topk_logprobs, beam_select
 
 __all__ = [
     "extension", "lstm_forward", "concat_pool", "StreamingConcatPool",
     "pool_head", "variational_dropout",
     "tied_decoder_ce", "TiedDecoderCE", "FusedAdamW",
-    "decode_logits", "sample_next", "topk_logprobs", "beam_select",
+    "decode_logits", "decode_cutoff", "sample_next", "topk_logprobs", "beam_select",
 ]

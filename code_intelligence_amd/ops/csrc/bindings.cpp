@@ -80,7 +80,10 @@ void decode_logits(at::Tensor h, at::Tensor weight,
                    at::Tensor partials);
 void decode_sample(at::Tensor logits, at::Tensor partials, at::Tensor u,
                    double temperature, double min_p, long unk,
-                   at::Tensor out_ids, at::Tensor out_logp);
+                   at::Tensor out_ids, at::Tensor out_logp,
+                   c10::optional<at::Tensor> cut);
+void decode_cutoff(at::Tensor logits, long k, double top_p, long unk,
+                   at::Tensor out);
 void topk_logprobs(at::Tensor logits, long k, long unk, at::Tensor out_vals,
                    at::Tensor out_idx);
 void beam_select(at::Tensor scores, at::Tensor vals, at::Tensor idx,
@@ -166,7 +169,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "output; writes id (int64) and temperature-1 log-prob per row",
         py::arg("logits"), py::arg("partials"), py::arg("u"),
         py::arg("temperature"), py::arg("min_p"), py::arg("unk"),
-        py::arg("out_ids"), py::arg("out_logp"));
+        py::arg("out_ids"), py::arg("out_logp"),
+        py::arg("cut") = py::none());
+  m.def("decode_cutoff", &ci::decode_cutoff,
+        "per row of fp32 logits the logit at which the top-k / nucleus set "
+        "ends (-inf: nothing filters); k = 0 / top_p = 0: that filter is off",
+        py::arg("logits"), py::arg("k"), py::arg("top_p"), py::arg("unk"),
+        py::arg("out"));
   m.def("topk_logprobs", &ci::topk_logprobs,
         "k largest log-probabilities of every row of logits, descending, "
         "ties to the lower index; unk is never returned",

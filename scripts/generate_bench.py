@@ -7,8 +7,12 @@ Compares, in one process and alternating between the two,
           masks + pow + torch.multinomial + .item() per word
 and reports the median over repeats, the spread of each, and the decode
 kernels' share of a word (the two K10 launches timed alone with device events).
+With --top_k / --top_p the fused loop samples through the top-k / nucleus
+filters (one more launch per word, decode_cutoff, also timed alone, next to
+decode_logits alone) and the eager loop adds torch.sort + cumsum + mask.
 
     python scripts/generate_bench.py [--repeats 7] [--words 64] [--prompt 32]
+                                     [--top_k K] [--top_p P]
 
 Prints one JSON line. Needs a GPU: there is no CPU fallback for a timing.
 """
@@ -25,7 +29,8 @@ import torch.nn.functional as F
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 
 
-def eager_generate(model, prompt, n_words, temperature, min_p, unk):
+def eager_generate(model, prompt, n_words, temperature, min_p, unk,
+                   top_k=None, top_p=None):
     lin = model.decoder.decoder
     out = []
     with torch.no_grad():
@@ -35,6 +40,15 @@ def eager_generate(model, prompt, n_words, temperature, min_p, unk):
             h = model.encoder(x)[1][-1][:, -1]
             res = F.softmax(F.linear(h, lin.weight, lin.bias).float(), dim=-1)
             res[:, unk] = 0.0
+            if top_k is not None or top_p is not None:
+                srt, order = torch.sort(res, dim=-1, descending=True)
+                drop = torch.zeros_like(srt, dtype=torch.bool)
+                if top_k is not None:
+                    drop[:, top_k:] = True
+                if top_p is not None:
+                    mass = srt.cumsum(dim=-1)
+                    drop |= (mass - srt) >= top_p * mass[:, -1:]
+                res.scatter_(1, order, srt.masked_fill(drop, 0.0))
             if min_p is not None and bool((res >= min_p).any().item()):
                 res[res < min_p] = 0.0
             if temperature != 1.0:
@@ -59,23 +73,30 @@ def main():
     ap.add_argument("--words", type=int, default=64)
     ap.add_argument("--prompt", type=int, default=32)
     ap.add_argument("--vocab", type=int, default=60000)
+    ap.add_argument("--top_k", type=int, default=None)
+    ap.add_argument("--top_p", type=float, default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("generate_bench needs a GPU")
     from code_intelligence_amd.models.awd_lstm import AWDLSTM
-    from code_intelligence_amd.ops import decode_logits, sample_next
+    from code_intelligence_amd.ops import (decode_cutoff, decode_logits,
+                                           sample_next)
+    filt = dict(top_k=args.top_k, top_p=args.top_p)
+    filtered = args.top_k is not None or args.top_p is not None
     dev = "cuda:0"
     torch.manual_seed(0)
     model = AWDLSTM(vocab_sz=args.vocab, emb_sz=800, n_hid=2400, n_layers=4) \
         .to(device=dev, dtype=torch.bfloat16).eval()
     lin = model.decoder.decoder
     result = {"shape": f"V{args.vocab} emb800 4x2400 bf16",
-              "prompt": args.prompt, "words": args.words, "rows": {}}
+              "prompt": args.prompt, "words": args.words, **filt,
+              "rows": {}}
     for B in (1, 8):
         prompt = torch.randint(10, args.vocab, (B, args.prompt), device=dev)
         fused = lambda: model.generate(prompt, args.words, temperature=0.8,
-                                       min_p=1e-4, seed=1)
-        eager = lambda: eager_generate(model, prompt, args.words, 0.8, 1e-4, 0)
+                                       min_p=1e-4, seed=1, **filt)
+        eager = lambda: eager_generate(model, prompt, args.words, 0.8, 1e-4, 0,
+                                       **filt)
         for _ in range(2):                  # warm every shape of both loops
             fused()
             eager()
@@ -87,19 +108,23 @@ def main():
         h = torch.randn(B, 800, device=dev).to(torch.bfloat16)
         u = torch.rand(B, device=dev)
         scratch = decode_logits(h, lin.weight, lin.bias)
-        for _ in range(10):
-            sample_next(h, lin.weight, lin.bias, u, 0.8, 1e-4, 0,
-                        scratch=scratch)
-        n = 200
-        e0, e1 = torch.cuda.Event(enable_timing=True), \
-            torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(n):
-            sample_next(h, lin.weight, lin.bias, u, 0.8, 1e-4, 0,
-                        scratch=scratch)
-        e1.record()
-        torch.cuda.synchronize()
-        k10 = e0.elapsed_time(e1) / n
+        cut = torch.empty(B, device=dev)
+
+        def alone(fn, n=200):
+            for _ in range(10):
+                fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), \
+                torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(n):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / n
+
+        k10 = alone(lambda: sample_next(h, lin.weight, lin.bias, u, 0.8, 1e-4,
+                                        0, scratch=scratch, cut_scratch=cut,
+                                        **filt))
         mf, me = statistics.median(tf), statistics.median(te)
         result["rows"][f"B{B}"] = {
             "fused_ms_per_word": round(mf, 4),
@@ -109,6 +134,13 @@ def main():
             "k10_ms_per_word": round(k10, 4),
             "k10_share_of_fused_word": round(k10 / mf, 3),
         }
+        if filtered:
+            result["rows"][f"B{B}"].update({
+                "cutoff_ms": round(alone(lambda: decode_cutoff(
+                    scratch[0], args.top_k, args.top_p, 0, out=cut)), 4),
+                "logits_ms": round(alone(lambda: decode_logits(
+                    h, lin.weight, lin.bias, out=scratch)), 4),
+            })
     print(json.dumps(result))
 
 
